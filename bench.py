@@ -13,6 +13,13 @@ Single GPU:      python bench.py --gpus 1 --steps 30 --warmup 5
 Multi GPU (driver launches):
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
       --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times exactly --steps steps and prints one
+JSON result line. --dump-outputs DIR additionally writes what the last timed
+step computed (see dump_outputs) so two builds can be compared output for
+output; inputs and initial weights are seeded, hence identical from run to
+run. --full is where any measurement beyond the headline figure belongs
+(nothing in this benchmark needs it yet, so it adds no work today).
 """
 from __future__ import annotations
 
@@ -22,6 +29,7 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -43,6 +51,13 @@ def parse():
                    help='collective | gather (PS engine fan-in mode)')
     p.add_argument('--engine', type=str, default='ps',
                    help='ps | allreduce (N>1 only)')
+    p.add_argument('--dump-outputs', type=str, default=None, metavar='DIR',
+                   help='after the timed steps write the last step\'s '
+                        'outputs to DIR/<name>.npy (float32)')
+    p.add_argument('--full', action='store_true',
+                   help='also run every secondary measurement or check '
+                        '(none exist yet; a plain run only times the '
+                        'headline figure)')
     return p.parse_args()
 
 
@@ -60,6 +75,41 @@ def make_batches(n_batches, bs, device, dtype, seed=1234,
         xs.append(x)
         ys.append(torch.randint(0, ncls, (bs,), generator=g).to(device))
     return xs, ys
+
+
+# --dump-outputs budget: 64 MB in all. Two large arrays (weights, grads) of
+# at most DUMP_MAX_ELEMS float32 each (2 x 28 MB) plus the scalar loss.
+DUMP_MAX_ELEMS = 7_000_000
+DUMP_SAMPLE_SEED = 20240607
+
+
+def _dump_array(t: torch.Tensor) -> np.ndarray:
+    """Flatten to float32 on the host; an array above DUMP_MAX_ELEMS is cut
+    to a fixed, seeded, sorted sample of its elements (same indices for the
+    same length, so two builds dump the same positions)."""
+    flat = t.detach().reshape(-1)
+    if flat.numel() > DUMP_MAX_ELEMS:
+        g = torch.Generator(device='cpu').manual_seed(DUMP_SAMPLE_SEED)
+        idx = torch.randperm(flat.numel(), generator=g)[:DUMP_MAX_ELEMS]
+        flat = flat[idx.sort().values.to(flat.device)]
+    return flat.to('cpu', torch.float32).numpy()
+
+
+def dump_outputs(out_dir, role, loss):
+    """Write what a caller of the timed step holds after the LAST timed
+    step: the loss it returned (where the role computes one), the updated
+    f32 master weights and the flat gradient buffer that step produced."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    if loss is not None:
+        arrays['loss'] = np.asarray([float(loss)], dtype=np.float32)
+    if getattr(role, 'master_w', None) is not None:
+        arrays['master_weights'] = _dump_array(role.master_w)
+    flat = getattr(role, 'flat', None)
+    if flat is not None and getattr(flat, 'flat_g', None) is not None:
+        arrays['grads'] = _dump_array(flat.flat_g)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
 
 
 def main():
@@ -147,6 +197,8 @@ def main():
                           device=device if env['backend'] == 'nccl' else 'cpu')
         dist.all_reduce(et, op=dist.ReduceOp.MAX)
         elapsed = float(et)
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, role, None)
         if args.engine == 'allreduce':
             n_workers = world
             parallelism = f"allreduce-dp ({world} ranks)"
@@ -175,11 +227,14 @@ def main():
         if use_cuda:
             torch.cuda.synchronize()
         t0 = time.time()
+        loss = None
         for i in range(args.steps):
-            step_fn(xs[i % len(xs)], ys[i % len(ys)])
+            loss = step_fn(xs[i % len(xs)], ys[i % len(ys)])
         if use_cuda:
             torch.cuda.synchronize()
         elapsed = time.time() - t0
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, tr, loss)
         imgs = args.batch_size * args.steps
         parallelism = "single-gpu"
         global_batch = args.batch_size

@@ -1953,6 +1953,57 @@ __global__ __launch_bounds__(256) void colsum_fold_kernel(
     if (threadIdx.x == 0) db[k] = f32_to_bf16(red[0]);
 }
 
+// dx seed for the strided dgrad: dst = src (or 0 when src == null) over n
+// bf16 elements. A kernel, not hipMemcpyAsync/hipMemsetAsync: captured into
+// a hipGraph those become memcpy/memset nodes, and on replay from an idle
+// queue their writes were observed to land after the kernels that follow
+// them in stream order (consumers read uninitialised dx -> NaN grads).
+// Kernel nodes keep stream order. 16-B vectors when both pointers allow;
+// each block moves U consecutive 4-KB chunks per iteration (U independent
+// loads in flight per lane), grid-striding over the rest.
+#ifndef PS_SEED_U
+#define PS_SEED_U 4
+#endif
+template <int U>
+__global__ __launch_bounds__(256) void seed_dx_kernel(
+    unsigned short* __restrict__ dst, const unsigned short* __restrict__ src,
+    long n, int vec_ok)
+{
+    const long nvec = vec_ok ? (n >> 3) : 0;
+    uint4* d4 = (uint4*)dst;
+    const uint4* s4 = (const uint4*)src;
+    const uint4 z = make_uint4(0u, 0u, 0u, 0u);
+    const long span = 256L * U;                  // vectors per block-iteration
+    for (long b0 = (long)blockIdx.x * span; b0 < nvec;
+         b0 += (long)gridDim.x * span) {
+        uint4 v[U];
+#pragma unroll
+        for (int k = 0; k < U; ++k) {
+            long i = b0 + k * 256 + threadIdx.x;
+            v[k] = (src && i < nvec) ? s4[i] : z;
+        }
+#pragma unroll
+        for (int k = 0; k < U; ++k) {
+            long i = b0 + k * 256 + threadIdx.x;
+            if (i < nvec) d4[i] = v[k];
+        }
+    }
+    EW_IDX
+    for (long i = (nvec << 3) + gid; i < n; i += stride)
+        dst[i] = src ? src[i] : (unsigned short)0;
+}
+
+static void launch_seed_dx(void* dst, const void* src, long n, void* strm)
+{
+    if (n <= 0) return;
+    int vec_ok = (((uintptr_t)dst | (uintptr_t)src) & 15) == 0;
+    int blocks;
+    ew_grid(vec_ok ? ((n + 7) >> 3) / PS_SEED_U + 1 : n, 256, &blocks);
+    hipLaunchKernelGGL(seed_dx_kernel<PS_SEED_U>, dim3(blocks), dim3(256), 0,
+                       (hipStream_t)strm, (unsigned short*)dst,
+                       (const unsigned short*)src, n, vec_ok);
+}
+
 // ---------------------------------------------------------------- C API
 
 // PS_SWZ=1 selects the round-1 LDS swizzle for on-hardware A/B (gswz).
@@ -2118,7 +2169,8 @@ extern "C" void ps_conv_dgrad(
     } else {
         // 4 parity-class launches (see conv_dgrad2_kernel); classes with no
         // contributing (r,s) — e.g. 3 of 4 for a 1x1 stride-2 conv — are
-        // covered by one bulk memset instead of scattered zero stores.
+        // covered by one bulk seed of dx (seed_dx_kernel) instead of
+        // scattered zero stores.
         const unsigned short* dout = (const unsigned short*)src;
         bool any_empty = false;
         for (int hp = 0; hp < 2 && hp < H; ++hp)
@@ -2126,16 +2178,9 @@ extern "C" void ps_conv_dgrad(
             int r0 = (hp + pad) & 1, s0 = (wp + pad) & 1;
             if (R <= r0 || S <= s0) any_empty = true;
         }
-        if (any_empty) {
-            // parity classes with no contributing taps: dx = carry (or 0)
-            if (carry)
-                (void)hipMemcpyAsync(dst, carry, (long)Nb * H * W * C * 2,
-                                     hipMemcpyDeviceToDevice,
-                                     (hipStream_t)strm);
-            else
-                (void)hipMemsetAsync(dst, 0, (long)Nb * H * W * C * 2,
-                                     (hipStream_t)strm);
-        }
+        // parity classes with no contributing taps: dx = carry (or 0)
+        if (any_empty)
+            launch_seed_dx(dst, carry, (long)Nb * H * W * C, strm);
         int TM_ = 128, TN_ = (C >= 128) ? 128 : 64;
         int tiles_n_ = (C + TN_ - 1) / TN_;
         int ends_[4] = {0, 0, 0, 0}, codes_[4] = {0, 0, 0, 0};

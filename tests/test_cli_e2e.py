@@ -18,6 +18,11 @@ def test_cli_train_checkpoint_evaluate(tmp_path):
     env = dict(os.environ)
     env.pop('RANK', None)
     env.pop('WORLD_SIZE', None)
+    # this is the CPU/gloo workflow: hide any GPUs from the child processes,
+    # otherwise a host with fewer GPUs than ranks picks RCCL and puts both
+    # ranks on one device
+    for var in ('HIP_VISIBLE_DEVICES', 'CUDA_VISIBLE_DEVICES'):
+        env[var] = ''
     out = subprocess.run(
         [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1',
          '--nproc-per-node', '2', '--master-addr', '127.0.0.1',

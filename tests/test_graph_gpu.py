@@ -39,6 +39,32 @@ def test_graph_step_matches_eager():
     assert d / scale < 1e-2, (d.item(), scale.item())
 
 
+def test_graph_replay_from_idle_queue_matches_back_to_back():
+    """A replay that starts on an idle GPU (host sync between replays, as
+    between a benchmark's warmup and timed steps) must compute what
+    back-to-back replays compute. Regression: the strided dgrad seeded dx
+    with memcpy/memset graph nodes whose writes landed late on replay from
+    an idle queue, so consumers read uninitialised dx and grads/weights
+    went NaN from the third synced replay on."""
+    tr_a, x, y = _mk()
+    assert tr_a.enable_graph(x, y)
+    for _ in range(4):
+        tr_a.graph_step(x, y)
+    torch.cuda.synchronize()
+
+    tr_b, x2, y2 = _mk()
+    assert tr_b.enable_graph(x2, y2)
+    for _ in range(4):
+        tr_b.graph_step(x2, y2)
+        torch.cuda.synchronize()
+    for tr in (tr_a, tr_b):
+        assert torch.isfinite(tr.master_w).all()
+        assert torch.isfinite(tr.flat.flat_g.float()).all()
+    d = (tr_a.master_w - tr_b.master_w).abs().max()
+    scale = tr_a.master_w.abs().max()
+    assert d / scale < 1e-2, (d.item(), scale.item())
+
+
 def test_graph_replay_updates_weights():
     tr, x, y = _mk()
     assert tr.enable_graph(x, y)

@@ -1,5 +1,6 @@
 """Tuning parser, speedup analysis, and autograd-driver parity components."""
 import json
+import os
 import subprocess
 import sys
 
@@ -9,6 +10,8 @@ import torch.nn.functional as F
 from ps_pytorch_amd.tuning_parser import parse_losses, main as tp_main
 from ps_pytorch_amd.utils.logging import worker_log_line
 from ps_pytorch_amd.utils.autograd import run_backward, loss_backward_via_logits
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_tuning_parser_roundtrip(tmp_path):
@@ -33,8 +36,9 @@ def test_speedup_analysis_bench_mode(tmp_path):
                                  'ms_per_step': ms}) + '\n')
         paths.append(str(p))
     out = subprocess.run(
-        [sys.executable, 'analysis/speedup.py', 'bench'] + paths,
-        capture_output=True, text=True, cwd='.')
+        [sys.executable, os.path.join(REPO, 'analysis', 'speedup.py'),
+         'bench'] + paths,
+        capture_output=True, text=True, cwd=REPO)
     assert out.returncode == 0, out.stderr
     assert '6.675' in out.stdout     # 660000/98876 speedup at N=8
 
