@@ -39,7 +39,9 @@ def add_fit_args(parser: argparse.ArgumentParser) -> argparse.ArgumentParser:
     parser.add_argument('--log-interval', type=int, default=10, metavar='N',
                         help='batches between log lines')
     parser.add_argument('--network', type=str, default='LeNet', metavar='N',
-                        help='LeNet | ResNet18/34/50/101/152 | VGG11/13/16/19[_BN]')
+                        help='LeNet | ResNet18/34/50/101/152 | '
+                             'VGG11/13/16/19[_BN|_plain][_ref] (_ref = the '
+                             'reference dropout classifier head)')
     parser.add_argument('--mode', type=str, default='normal', metavar='N',
                         help='normal | kill | timeout : straggler handling '
                              '(kill = PS signal on quota, ref backward_signal_kill; '

@@ -6,6 +6,7 @@ import torch.nn as nn
 from .lenet import LeNet
 from .resnet import ResNet18, ResNet34, ResNet50, ResNet101, ResNet152
 from .vgg import VGG11, VGG11_BN, VGG13, VGG13_BN, VGG16, VGG16_BN, VGG19, VGG19_BN
+from .vgg import REF_FACTORY, convert_reference_vgg_state_dict
 
 _FACTORY = {
     'lenet': LeNet,
@@ -28,6 +29,9 @@ _FACTORY = {
     'vgg19_plain': VGG19,
     'vgg19': VGG19_BN,
     'vgg19_bn': VGG19_BN,
+    # opt-in reference classifier head (Dropout/Linear/ReLU x2 + Linear,
+    # ref model_ops/vgg.py:22-30): vggNN_ref, vggNN_bn_ref, vggNN_plain_ref
+    **REF_FACTORY,
 }
 
 
@@ -50,4 +54,5 @@ def build_model(name: str, num_classes: int = 10, in_channels: int = 3) -> nn.Mo
 
 __all__ = ['build_model', 'LeNet', 'ResNet18', 'ResNet34', 'ResNet50',
            'ResNet101', 'ResNet152', 'VGG11', 'VGG13', 'VGG16', 'VGG19',
-           'VGG11_BN', 'VGG13_BN', 'VGG16_BN', 'VGG19_BN']
+           'VGG11_BN', 'VGG13_BN', 'VGG16_BN', 'VGG19_BN',
+           'convert_reference_vgg_state_dict']

@@ -86,6 +86,15 @@ def _try_load() -> None:
         lib.ps_padc.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
                                 ctypes.c_long, ctypes.c_int, ctypes.c_int,
                                 ctypes.c_void_p]
+        # y, mask, x, n, dtype, relu, thr, scale, seed, salt_stream,
+        # step_ptr, stream
+        lib.ps_act_drop_fwd.argtypes = [ctypes.c_void_p] * 3 + [
+            ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_uint32,
+            ctypes.c_float, ctypes.c_uint64, ctypes.c_uint32,
+            ctypes.c_void_p, ctypes.c_void_p]
+        lib.ps_act_drop_bwd.argtypes = [ctypes.c_void_p] * 3 + [
+            ctypes.c_long, ctypes.c_int, ctypes.c_float, ctypes.c_void_p]
+        lib.ps_rng_advance.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         _LIB = lib
     except OSError as e:  # pragma: no cover
         _LIB_ERR = str(e)

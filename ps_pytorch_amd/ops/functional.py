@@ -216,3 +216,104 @@ def acc_into(acc: torch.Tensor, src: torch.Tensor) -> None:
                              dtype_tag(src.dtype), current_stream_ptr())
         return
     acc.add_(src.to(torch.float32))
+
+
+# ---- counter-based dropout (CPU oracle for ops/kernels/dropout.hip) ----
+# Philox4x32-10; element e takes word (e & 3) of the block whose counter is
+# (lo32(e>>2), hi32(e>>2), step, (stream << 16) | salt) under key
+# (lo32(seed), hi32(seed)); keep iff word >= round(p * 2^32). Everything is
+# integer arithmetic, so the masks equal the kernel's bit for bit.
+
+_PHILOX_M0, _PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
+_PHILOX_W0, _PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
+_U32 = 0xFFFFFFFF
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10 on uint32 words: counter [..., 4], key [..., 2] (numpy
+    broadcastable) -> uint32 [..., 4]."""
+    import numpy as np
+    c = np.asarray(counter, dtype=np.uint64) & np.uint64(_U32)
+    k = np.asarray(key, dtype=np.uint64) & np.uint64(_U32)
+    c0, c1, c2, c3 = c[..., 0], c[..., 1], c[..., 2], c[..., 3]
+    k0, k1 = k[..., 0], k[..., 1]
+    m32 = np.uint64(_U32)
+    s32 = np.uint64(32)
+    for _ in range(10):
+        p0 = np.uint64(_PHILOX_M0) * c0     # 32x32 -> 64: exact in uint64
+        p1 = np.uint64(_PHILOX_M1) * c2
+        c0, c1, c2, c3 = ((p1 >> s32) ^ c1 ^ k0, p1 & m32,
+                          (p0 >> s32) ^ c3 ^ k1, p0 & m32)
+        k0 = (k0 + np.uint64(_PHILOX_W0)) & m32
+        k1 = (k1 + np.uint64(_PHILOX_W1)) & m32
+    return np.stack(np.broadcast_arrays(c0, c1, c2, c3),
+                    axis=-1).astype(np.uint32)
+
+
+def dropout_threshold(p: float) -> int:
+    """thr = round(p * 2^32) as a uint32: keep iff word >= thr. 0 keeps
+    everything; p >= 1 is not representable and is handled by the callers."""
+    return min(max(int(round(float(p) * 4294967296.0)), 0), _U32)
+
+
+def dropout_salt_stream(salt: int, stream: int) -> int:
+    return ((int(stream) & 0xFFFF) << 16) | (int(salt) & 0xFFFF)
+
+
+def dropout_keep_mask(n: int, p: float, seed: int, salt: int = 0,
+                      stream: int = 0, step: int = 0) -> torch.Tensor:
+    """bool [n]: True where the dropout kernel keeps element e."""
+    import numpy as np
+    if p >= 1.0:
+        return torch.zeros(n, dtype=torch.bool)
+    thr = dropout_threshold(p)
+    if thr == 0:
+        return torch.ones(n, dtype=torch.bool)
+    blk = np.arange((n + 3) // 4, dtype=np.uint64)
+    ctr = np.empty((blk.size, 4), dtype=np.uint64)
+    ctr[:, 0] = blk & np.uint64(_U32)
+    ctr[:, 1] = blk >> np.uint64(32)
+    ctr[:, 2] = int(step) & _U32
+    ctr[:, 3] = dropout_salt_stream(salt, stream)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    words = philox4x32_10(ctr, [seed & _U32, seed >> 32]).reshape(-1)[:n]
+    return torch.from_numpy(words >= np.uint32(thr))
+
+
+def dropout_scale(p: float) -> float:
+    """float32(1/(1-p)); 0.0 encodes p >= 1 (everything dropped)."""
+    if p >= 1.0:
+        return 0.0
+    return float(torch.tensor(1.0 / (1.0 - float(p)), dtype=torch.float32))
+
+
+def act_drop_ref(x: torch.Tensor, keep: torch.Tensor, scale: float,
+                 relu: bool):
+    """Reference forward of the act-drop kernel: returns (y, bits) with
+    y = bits ? T(float(x) * scale) : 0 and bits = keep & (!relu | x > 0),
+    in the kernel's order (float32 multiply, then round to x.dtype)."""
+    xf = x.detach().to(torch.float32)
+    bits = keep.reshape(x.shape).to(x.device)
+    if relu:
+        bits = bits & (xf > 0)
+    s = torch.tensor(scale, dtype=torch.float32, device=x.device)
+    y = torch.where(bits, (xf * s).to(x.dtype), torch.zeros((), dtype=x.dtype,
+                                                           device=x.device))
+    return y, bits
+
+
+def act_drop_bwd_ref(dy: torch.Tensor, bits: torch.Tensor,
+                     scale: float) -> torch.Tensor:
+    """dx = bits ? T(float(dy) * scale) : 0."""
+    s = torch.tensor(scale, dtype=torch.float32, device=dy.device)
+    dx = (dy.to(torch.float32) * s).to(dy.dtype)
+    return torch.where(bits.reshape(dy.shape), dx,
+                       torch.zeros((), dtype=dy.dtype, device=dy.device))
+
+
+def pack_mask_bits(bits: torch.Tensor) -> torch.Tensor:
+    """bool [n] -> uint8 [(n+7)//8] in the kernels' layout (bit k of byte i
+    is element 8*i+k)."""
+    import numpy as np
+    b = bits.reshape(-1).cpu().numpy()
+    return torch.from_numpy(np.packbits(b, bitorder='little'))

@@ -1140,7 +1140,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(
 // staged byte of the generic kernel, and dout/in leave L2 R times instead
 // of R*S times. Requires: stride 1, R=S=3, pad 1 (so H=P, W=Q and the
 // (n*H+h) axis is globally linear in the output row index), Q a power of
-// two <= 32, P a power of two.
+// two in [4, 32] (the B halo image holds 48 pixels; a step stages
+// ROWS * (Q + 2) = 32 + 64/Q), P a power of two.
 //
 // Contraction axis = 32 consecutive output pixels (exactly one
 // mfma_f32_16x16x32 depth): ROWS = 32/Q output rows per step; each lane's
@@ -2273,8 +2274,13 @@ extern "C" void ps_conv_wgrad(
         static int row_en = -1;
         if (row_en < 0) row_en = getenv("PS_WG_ROW_OFF") ? 0 : 1;
         int l2q_ = ilog2_exact(Q), l2pq_ = ilog2_exact((long)P * Q);
+        // Q >= 4: a step stages ROWS * (Q + 2) = 32 + 64/Q halo pixels and
+        // the kernels' LDS B image holds 48 — at Q = 2 (VGG's last conv
+        // stage) the writes ran past their c-subtile into the next one, a
+        // write race: wrong and run-to-run different dw. Those shapes take
+        // the generic kernel.
         if (row_en && stride == 1 && R == 3 && S == 3 && pad == 1 && P == H
-            && Q == W && l2q_ >= 0 && l2pq_ >= 0 && Q <= 32) {
+            && Q == W && l2q_ >= 0 && l2pq_ >= 0 && Q >= 4 && Q <= 32) {
             static int wg_glds = -1;
             if (wg_glds < 0) {
                 const char* e = getenv("PS_WG_GLDS");

@@ -18,6 +18,7 @@ from typing import Optional
 
 import torch
 
+from ..ops.dropout import PsDropout
 from ..ops.loss import cross_entropy as ps_cross_entropy
 
 from ..config import JobConfig, input_shape_of, num_classes_of
@@ -61,6 +62,11 @@ class DistributedWorker:
         torch.manual_seed(cfg.seed)   # same init on every rank
         net = build_model(cfg.network, num_classes=nc, in_channels=in_ch)
         net = prep_model(net, self.device, self.compute_dtype)
+        # same init everywhere, but each data-parallel replica draws its own
+        # dropout masks
+        for m in net.modules():
+            if isinstance(m, PsDropout):
+                m.stream = self.rank
         self.network = net
         self.flat = FlatSpace(net, bucket_bytes=int(cfg.bucket_mb * 2 ** 20))
         self.flat.attach_grads(steal=(self.device.type == 'cuda'))
