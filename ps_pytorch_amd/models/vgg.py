@@ -8,7 +8,7 @@ from ..ops.conv import PsConv2d
 from ..ops.dropout import PsDropout, PsReLU
 from ..ops.linear import PsLinear
 from ..ops.modules import PsBatchNorm2d
-from ..ops.pool import max_pool2d as ps_max_pool2d
+from ..ops.pool import max_pool2d as ps_max_pool2d, global_avg_pool
 
 
 class PsMaxPool2d(nn.Module):
@@ -22,6 +22,16 @@ class PsMaxPool2d(nn.Module):
 
     def forward(self, x):
         return ps_max_pool2d(x, self.kernel_size, self.stride)
+
+
+class PsGlobalAvgPool2d(nn.Module):
+    """nn.AdaptiveAvgPool2d(1) on the in-tree NHWC kernels (torch fallback
+    on CPU): [N,C,H,W] -> [N,C,1,1]. Parameter-free, so it keeps the
+    reference's features index without touching the state_dict."""
+
+    def forward(self, x):
+        return global_avg_pool(x)[:, :, None, None]
+
 
 _CFG = {
     'VGG11': [64, 'M', 128, 'M', 256, 256, 'M', 512, 512, 'M', 512, 512, 'M'],
@@ -46,7 +56,7 @@ def _make_layers(cfg, in_channels: int, batch_norm: bool) -> nn.Sequential:
             else:
                 layers.append(PsReLU())
             c = v
-    layers.append(nn.AdaptiveAvgPool2d(1))
+    layers.append(PsGlobalAvgPool2d())
     return nn.Sequential(*layers)
 
 

@@ -23,6 +23,15 @@ PS_BF16 = 1
 
 _DTYPE_TAG = {torch.float32: PS_F32, torch.bfloat16: PS_BF16}
 
+# entry points of the f32 kernel family (--compute-dtype fp32 on the GPU)
+F32_SYMBOLS = (
+    'ps_conv_fwd_f32', 'ps_conv_dgrad_f32', 'ps_conv_wgrad_f32',
+    'ps_conv_bias_grad_f32',
+    'ps_maxpool_fwd_f32', 'ps_maxpool_bwd_f32',
+    'ps_gavgpool_fwd_f32', 'ps_gavgpool_bwd_f32',
+    'ps_softmax_ce_fwd_f32', 'ps_softmax_ce_bwd_f32',
+)
+
 
 def _so_path() -> Path:
     return Path(__file__).resolve().parent / "libps_hip.so"
@@ -95,6 +104,18 @@ def _try_load() -> None:
         lib.ps_act_drop_bwd.argtypes = [ctypes.c_void_p] * 3 + [
             ctypes.c_long, ctypes.c_int, ctypes.c_float, ctypes.c_void_p]
         lib.ps_rng_advance.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        # f32 family (conv_f32.hip + the f32 twins in pool / softmaxce)
+        lib.ps_conv_fwd_f32.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int] * 11 + [ctypes.c_void_p]
+        lib.ps_conv_dgrad_f32.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int] * 11 + [ctypes.c_void_p]
+        lib.ps_conv_wgrad_f32.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int] * 12 + [ctypes.c_void_p]
+        lib.ps_conv_bias_grad_f32.argtypes = [ctypes.c_void_p] * 3 + [
+            ctypes.c_long, ctypes.c_int, ctypes.c_void_p]
+        lib.ps_softmax_ce_fwd_f32.argtypes = lib.ps_softmax_ce_fwd.argtypes
+        lib.ps_softmax_ce_bwd_f32.argtypes = lib.ps_softmax_ce_bwd.argtypes
+        lib.ps_maxpool_fwd_f32.argtypes = lib.ps_maxpool_fwd.argtypes
+        lib.ps_maxpool_bwd_f32.argtypes = lib.ps_maxpool_bwd.argtypes
+        lib.ps_gavgpool_fwd_f32.argtypes = lib.ps_gavgpool_fwd.argtypes
+        lib.ps_gavgpool_bwd_f32.argtypes = lib.ps_gavgpool_bwd.argtypes
         _LIB = lib
     except OSError as e:  # pragma: no cover
         _LIB_ERR = str(e)

@@ -1,4 +1,5 @@
-"""PsConv2d — NHWC implicit-GEMM MFMA convolution (ops/kernels/conv.hip).
+"""PsConv2d — NHWC implicit-GEMM MFMA convolution (ops/kernels/conv.hip for
+bf16, ops/kernels/conv_f32.hip for fp32).
 
 Replaces the MIOpen path the reference reaches through nn.Conv2d
 (ref: src/model_ops/resnet.py:19-97, lenet.py:19-33). GPU training path is
@@ -38,11 +39,25 @@ def _pop_stats():
     return st
 
 
+# PS_F32=0 sends fp32 tensors back to torch (MIOpen / Tensile / at::native)
+# in every Ps op, for A/B against the exact-f32 kernel family
+# (ops/kernels/conv_f32.hip and the f32 twins in pool / softmaxce). The
+# per-op switches (PS_CONV, PS_LINEAR, PS_POOL, PS_CE) gate both dtypes.
+_F32 = os.environ.get('PS_F32', '1') != '0'
+
+
+def _dtype_ok(dt: torch.dtype) -> bool:
+    """Compute dtypes with a hand-kernel path (shared by every Ps op)."""
+    return dt == torch.bfloat16 or (dt == torch.float32 and _F32)
+
+
 def _supported(x: torch.Tensor, w: torch.Tensor, stride, padding,
                dilation, groups) -> bool:
     if not _ENABLED:
         return False
-    if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.bfloat16):
+    if not (x.is_cuda and x.dim() == 4 and _dtype_ok(x.dtype)):
+        return False
+    if x.dtype == torch.float32 and w.dtype != torch.float32:
         return False
     if groups != 1 or dilation[0] != 1 or dilation[1] != 1:
         return False
@@ -105,9 +120,98 @@ def _pad_rows(lib, src: torch.Tensor, nrows: int, K: int, Kp: int):
     return dst
 
 
+def _wgrad_split_f32(M: int, K: int, RSC: int) -> int:
+    """Split-K factor of the f32 wgrad (conv_f32.hip: 64x64 output tiles
+    over [K, R*S*C], contraction M = Nb*P*Q): ~2 blocks/CU on 256 CUs, at
+    least 64 contraction rows per slab. The one place this rule lives —
+    the kernel takes `split` as given and derives the slab length."""
+    tiles = ((K + 63) // 64) * ((RSC + 63) // 64)
+    want = max(1, 512 // max(tiles, 1))
+    return max(1, min(want, max(1, M // 64), 256))
+
+
+def _f32_bias_grad(lib, dy: torch.Tensor, M: int, K: int, b_tgt):
+    """db = column sum of dy[M, K] (f32), into the steal target if any."""
+    db = (b_tgt if b_tgt is not None and b_tgt.dtype == dy.dtype
+          and b_tgt.is_cuda
+          else torch.empty(K, dtype=dy.dtype, device=dy.device))
+    bpart = torch.empty(256 * K, dtype=torch.float32, device=dy.device)
+    lib.ps_conv_bias_grad_f32(db.data_ptr(), dy.data_ptr(),
+                              bpart.data_ptr(), M, K, current_stream_ptr())
+    return db
+
+
+def _f32_wgrad(lib, dy, x, dw, Nb, H, W, C, K, P, Q, R, S, stride, pad):
+    split = _wgrad_split_f32(Nb * P * Q, K, R * S * C)
+    partial = torch.empty(split * K * R * S * C if split > 1 else 1,
+                          dtype=torch.float32, device=x.device)
+    lib.ps_conv_wgrad_f32(dy.data_ptr(), x.data_ptr(), partial.data_ptr(),
+                          dw.data_ptr(), Nb, H, W, C, K, P, Q, R, S,
+                          stride, pad, split, current_stream_ptr())
+
+
+def _conv_f32_forward(ctx, x, w, b, stride, pad):
+    """f32 path: the exact-f32 MFMA family at the nominal C and K — no
+    padc, no row padding, no BN-stats handshake."""
+    lib = require_lib()
+    x = x.contiguous(memory_format=_CL)
+    wc = w.contiguous(memory_format=_CL)
+    Nb, C, H, W = x.shape
+    K, _, R, S = w.shape
+    P = (H + 2 * pad - R) // stride + 1
+    Q = (W + 2 * pad - S) // stride + 1
+    out = torch.empty((Nb, K, P, Q), dtype=x.dtype, device=x.device,
+                      memory_format=_CL)
+    lib.ps_conv_fwd_f32(x.data_ptr(), wc.data_ptr(),
+                        b.data_ptr() if b is not None else 0, out.data_ptr(),
+                        Nb, H, W, C, K, P, Q, R, S, stride, pad,
+                        current_stream_ptr())
+    ctx.save_for_backward(x, wc)
+    ctx.conf = (stride, pad, b is not None)
+    ctx.gtgt = (getattr(w, '_ps_flat_grad_fn', None),
+                getattr(b, '_ps_flat_grad_fn', None) if b is not None else None)
+    return out
+
+
+def _conv_f32_backward(ctx, dout, dcarry):
+    lib = require_lib()
+    x, w = ctx.saved_tensors
+    stride, pad, has_bias = ctx.conf
+    dout = dout.contiguous(memory_format=_CL)
+    Nb, C, H, W = x.shape
+    K, _, R, S = w.shape
+    P, Q = dout.shape[2], dout.shape[3]
+    dx = dw = db = None
+    if ctx.needs_input_grad[0]:
+        # dgrad gathers w[K,R,S,C] in place (no transposed copy) and adds
+        # the residual-fork gradient in its epilogue
+        dx = torch.empty((Nb, C, H, W), dtype=x.dtype, device=x.device,
+                         memory_format=_CL)
+        if dcarry is not None:
+            dcarry = dcarry.contiguous(memory_format=_CL)
+        lib.ps_conv_dgrad_f32(dout.data_ptr(), w.data_ptr(), dx.data_ptr(),
+                              dcarry.data_ptr() if dcarry is not None else 0,
+                              Nb, H, W, C, K, P, Q, R, S, stride, pad,
+                              current_stream_ptr())
+    if ctx.needs_input_grad[1]:
+        wt_tgt = ctx.gtgt[0]() if ctx.gtgt[0] is not None else None
+        dw = (wt_tgt if wt_tgt is not None and wt_tgt.dtype == w.dtype
+              and wt_tgt.is_cuda
+              else torch.empty((K, C, R, S), dtype=w.dtype, device=w.device,
+                               memory_format=_CL))
+        _f32_wgrad(lib, dout, x, dw, Nb, H, W, C, K, P, Q, R, S, stride, pad)
+    if has_bias and ctx.needs_input_grad[2]:
+        b_tgt = ctx.gtgt[1]() if ctx.gtgt[1] is not None else None
+        db = _f32_bias_grad(lib, dout, Nb * P * Q, K, b_tgt)
+    return dx, dw, db, None, None
+
+
 class _ConvFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, b, stride, pad):
+        ctx.f32 = x.dtype == torch.float32
+        if ctx.f32:
+            return _conv_f32_forward(ctx, x, w, b, stride, pad)
         lib = require_lib()
         x = x.contiguous(memory_format=_CL)
         wc = w.contiguous(memory_format=_CL)
@@ -189,6 +293,8 @@ class _ConvFn(torch.autograd.Function):
     def backward(ctx, dout, dcarry=None):
         """Shared by _ConvFn (dcarry always None) and _ConvCarryFn (dcarry =
         the residual path's gradient w.r.t. x, fused into the dx epilogue)."""
+        if ctx.f32:
+            return _conv_f32_backward(ctx, dout, dcarry)
         lib = require_lib()
         x, w = ctx.saved_tensors
         stride, pad, has_bias = ctx.conf
@@ -332,7 +438,9 @@ def conv_with_passthrough(mod: nn.Conv2d, x: torch.Tensor):
 
 
 class PsConv2d(nn.Conv2d):
-    """nn.Conv2d whose GPU bf16 path runs the in-tree CDNA4 kernels.
+    """nn.Conv2d whose GPU path runs the in-tree CDNA4 kernels: bf16 on
+    conv.hip, fp32 on the exact-f32 MFMA family in conv_f32.hip (which
+    ignores out_pad and runs at the nominal channel counts).
 
     Ragged-channel pipelines (LeNet's 20 -> 50) can stay 8-aligned end to
     end via `out_pad` (plain attr, default 0, not in state_dict): on the
@@ -349,6 +457,12 @@ class PsConv2d(nn.Conv2d):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         w, b = self.weight, self.bias
+        if x.dtype == torch.float32 and _supported(
+                x, w, self.stride, self.padding, self.dilation, self.groups):
+            # f32 rows are always 4-B aligned: nominal channels, no out_pad
+            if x.shape[1] != self.in_channels:
+                x = x[:, :self.in_channels]
+            return _ConvFn.apply(x, w, b, self.stride[0], self.padding[0])
         if _supported(x, w, self.stride, self.padding,
                       self.dilation, self.groups):
             cin = x.shape[1]

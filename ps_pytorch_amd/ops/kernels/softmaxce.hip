@@ -153,3 +153,113 @@ extern "C" void ps_softmax_ce_bwd(
                        (const float*)lse, (const long*)target,
                        (const float*)dloss, M, C);
 }
+
+// ======================= f32 twins (--compute-dtype fp32) ===================
+// Same wave-per-row structure and deterministic single-block fold as above,
+// on f32 logits. The op is memory-bound and tiny, so the row math (exp, log,
+// the row fold and the mean) runs in f64 and rounds ONCE to f32 at each
+// output: loss and dlogits are the correctly rounded values of the exact
+// expression, which is what lets the tests hold them against a float64
+// reference. lse / row_ws are therefore [M] f64 workspaces here.
+// Loads are 4-B per lane (coalesced across the wave): an f32 row start is
+// only 4-B aligned for a general C.
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int m = 32; m; m >>= 1)
+        v += __shfl_xor(v, m);
+    return v;
+}
+
+__global__ __launch_bounds__(256) void softmax_ce_fwd_f32_kernel(
+    double* __restrict__ row_ws,           // [M] per-row loss
+    double* __restrict__ lse,              // [M]
+    const float* __restrict__ x,           // [M, C] f32
+    const long* __restrict__ target,       // [M]
+    long M, int C)
+{
+    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= M) return;
+    const int lane = threadIdx.x & 63;
+    const float* xr = x + row * C;
+
+    float mx = -INFINITY;
+    for (int c = lane; c < C; c += 64) mx = fmaxf(mx, xr[c]);
+    mx = wave_max(mx);
+
+    double s = 0.0;
+    for (int c = lane; c < C; c += 64) s += exp((double)xr[c] - (double)mx);
+    s = wave_sum_f64(s);
+
+    if (lane == 0) {
+        double l = (double)mx + log(s);
+        lse[row] = l;
+        long t = target[row];
+        row_ws[row] = l - (double)xr[t];
+    }
+}
+
+__global__ __launch_bounds__(256) void rowloss_fold_f32_kernel(
+    float* __restrict__ loss, const double* __restrict__ row_ws, long M)
+{
+    __shared__ double red[256];
+    double acc = 0.0;
+    for (long i = threadIdx.x; i < M; i += 256) acc += row_ws[i];
+    red[threadIdx.x] = acc;
+    __syncthreads();
+#pragma unroll
+    for (int w = 128; w; w >>= 1) {
+        if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) loss[0] = (float)(red[0] / (double)M);
+}
+
+__global__ __launch_bounds__(256) void softmax_ce_bwd_f32_kernel(
+    float* __restrict__ dx,                // [M, C] f32
+    const float* __restrict__ x,           // [M, C] f32
+    const double* __restrict__ lse,        // [M]
+    const long* __restrict__ target,       // [M]
+    const float* __restrict__ dloss,       // [1]
+    long M, int C)
+{
+    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= M) return;
+    const int lane = threadIdx.x & 63;
+    const double g = (double)dloss[0] / (double)M;
+    const double l = lse[row];
+    const long t = target[row];
+    const float* xr = x + row * C;
+    float* dr = dx + row * C;
+    for (int c = lane; c < C; c += 64) {
+        double p = exp((double)xr[c] - l);
+        dr[c] = (float)((p - (c == t ? 1.0 : 0.0)) * g);
+    }
+}
+
+// lse, row_ws: [M] f64 workspaces (see above)
+extern "C" void ps_softmax_ce_fwd_f32(
+    void* loss, void* lse, void* row_ws, const void* logits,
+    const void* target, long M, int C, void* strm)
+{
+    long blocks = (M + 3) / 4;
+    hipLaunchKernelGGL(softmax_ce_fwd_f32_kernel, dim3((unsigned)blocks),
+                       dim3(256), 0, (hipStream_t)strm,
+                       (double*)row_ws, (double*)lse,
+                       (const float*)logits, (const long*)target, M, C);
+    hipLaunchKernelGGL(rowloss_fold_f32_kernel, dim3(1), dim3(256), 0,
+                       (hipStream_t)strm, (float*)loss,
+                       (const double*)row_ws, M);
+}
+
+extern "C" void ps_softmax_ce_bwd_f32(
+    void* dx, const void* logits, const void* lse, const void* target,
+    const void* dloss, long M, int C, void* strm)
+{
+    long blocks = (M + 3) / 4;
+    hipLaunchKernelGGL(softmax_ce_bwd_f32_kernel, dim3((unsigned)blocks),
+                       dim3(256), 0, (hipStream_t)strm,
+                       (float*)dx, (const float*)logits,
+                       (const double*)lse, (const long*)target,
+                       (const float*)dloss, M, C);
+}

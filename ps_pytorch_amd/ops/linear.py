@@ -1,4 +1,5 @@
-"""PsLinear — bf16 MFMA GEMM Linear on the in-tree CDNA4 kernels.
+"""PsLinear — MFMA GEMM Linear on the in-tree CDNA4 kernels (bf16, and
+fp32 on the exact-f32 MFMA family).
 
 Replaces the Tensile/rocBLAS GEMMs the reference reaches through nn.Linear
 (ref: src/model_ops/lenet.py:29-33 fc layers, resnet.py:100-103 classifier).
@@ -27,6 +28,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import require_lib, current_stream_ptr
+from . import conv as _conv
 from .conv import _PADK, _pad_rows, _pad_target, _wgrad_split
 
 # A/B kill-switch: PS_LINEAR=0 routes through torch (Tensile) GEMMs.
@@ -34,13 +36,63 @@ _ENABLED = os.environ.get('PS_LINEAR', '1') != '0'
 
 
 def _supported(x: torch.Tensor, w: torch.Tensor) -> bool:
-    return (_ENABLED and x.is_cuda and x.dtype == torch.bfloat16
-            and w.dtype == torch.bfloat16)
+    return (_ENABLED and x.is_cuda and w.dtype == x.dtype
+            and (x.dtype == torch.bfloat16
+                 or (x.dtype == torch.float32 and _conv._F32)))
+
+
+def _linear_f32_forward(ctx, x, w, b):
+    """f32: the same 1x1-conv mapping on the exact-f32 MFMA entry points
+    (ops/kernels/conv_f32.hip), at the nominal N — no row padding."""
+    lib = require_lib()
+    shape = x.shape
+    x2 = x.reshape(-1, shape[-1]).contiguous()
+    wc = w.contiguous()
+    M, K = x2.shape
+    N = wc.shape[0]
+    y = torch.empty((M, N), dtype=x.dtype, device=x.device)
+    lib.ps_conv_fwd_f32(x2.data_ptr(), wc.data_ptr(),
+                        b.data_ptr() if b is not None else 0, y.data_ptr(),
+                        M, 1, 1, K, N, 1, 1, 1, 1, 1, 0,
+                        current_stream_ptr())
+    ctx.save_for_backward(x2, wc)
+    ctx.conf = (shape, b is not None)
+    ctx.gtgt = (getattr(w, '_ps_flat_grad_fn', None),
+                getattr(b, '_ps_flat_grad_fn', None) if b is not None else None)
+    return y.reshape(*shape[:-1], N)
+
+
+def _linear_f32_backward(ctx, dout):
+    lib = require_lib()
+    x, w = ctx.saved_tensors
+    shape, has_bias = ctx.conf
+    M, K = x.shape
+    N = w.shape[0]
+    dy = dout.reshape(M, N).contiguous()
+    dx = dw = db = None
+    if ctx.needs_input_grad[0]:
+        dx = torch.empty_like(x)
+        lib.ps_conv_dgrad_f32(dy.data_ptr(), w.data_ptr(), dx.data_ptr(), 0,
+                              M, 1, 1, K, N, 1, 1, 1, 1, 1, 0,
+                              current_stream_ptr())
+        dx = dx.reshape(shape)
+    if ctx.needs_input_grad[1]:
+        wt_tgt = ctx.gtgt[0]() if ctx.gtgt[0] is not None else None
+        dw = (wt_tgt if wt_tgt is not None and wt_tgt.dtype == w.dtype
+              and wt_tgt.is_cuda else torch.empty_like(w))
+        _conv._f32_wgrad(lib, dy, x, dw, M, 1, 1, K, N, 1, 1, 1, 1, 1, 0)
+    if has_bias and ctx.needs_input_grad[2]:
+        b_tgt = ctx.gtgt[1]() if ctx.gtgt[1] is not None else None
+        db = _conv._f32_bias_grad(lib, dy, M, N, b_tgt)
+    return dx, dw, db
 
 
 class _LinearFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, b):
+        ctx.f32 = x.dtype == torch.float32
+        if ctx.f32:
+            return _linear_f32_forward(ctx, x, w, b)
         lib = require_lib()
         shape = x.shape
         x2 = x.reshape(-1, shape[-1]).contiguous()
@@ -61,6 +113,8 @@ class _LinearFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
+        if ctx.f32:
+            return _linear_f32_backward(ctx, dout)
         lib = require_lib()
         x, w = ctx.saved_tensors
         shape, has_bias = ctx.conf
@@ -131,7 +185,7 @@ class _LinearFn(torch.autograd.Function):
 
 
 class PsLinear(nn.Linear):
-    """nn.Linear whose GPU bf16 path runs the in-tree CDNA4 MFMA GEMMs."""
+    """nn.Linear whose GPU bf16 / fp32 path runs the in-tree CDNA4 MFMA GEMMs."""
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if _supported(x, self.weight):

@@ -13,6 +13,7 @@ import torch
 import torch.nn.functional as F
 
 from . import require_lib, current_stream_ptr
+from . import conv as _conv
 
 _CL = torch.channels_last
 _ENABLED = os.environ.get('PS_POOL', '1') != '0'
@@ -20,7 +21,12 @@ _ENABLED = os.environ.get('PS_POOL', '1') != '0'
 
 def _supported(x: torch.Tensor) -> bool:
     return (_ENABLED and x.is_cuda and x.dim() == 4
-            and x.dtype == torch.bfloat16)
+            and _conv._dtype_ok(x.dtype))
+
+
+def _entry(lib, name: str, dt: torch.dtype):
+    """bf16 entry point, or its f32 twin."""
+    return getattr(lib, name + '_f32' if dt == torch.float32 else name)
 
 
 class _MaxPoolFn(torch.autograd.Function):
@@ -34,7 +40,7 @@ class _MaxPoolFn(torch.autograd.Function):
         y = torch.empty((Nb, C, P, Q), dtype=x.dtype, device=x.device,
                         memory_format=_CL)
         arg = torch.empty(Nb * P * Q * C, dtype=torch.uint8, device=x.device)
-        lib.ps_maxpool_fwd(y.data_ptr(), arg.data_ptr(), x.data_ptr(),
+        _entry(lib, 'ps_maxpool_fwd', x.dtype)(y.data_ptr(), arg.data_ptr(), x.data_ptr(),
                            Nb, H, W, C, P, Q, k, k, stride, pad,
                            current_stream_ptr())
         ctx.save_for_backward(arg)
@@ -49,7 +55,7 @@ class _MaxPoolFn(torch.autograd.Function):
         dy = dy.contiguous(memory_format=_CL)
         dx = torch.empty((Nb, C, H, W), dtype=dy.dtype, device=dy.device,
                          memory_format=_CL)
-        lib.ps_maxpool_bwd(dx.data_ptr(), dy.data_ptr(), arg.data_ptr(),
+        _entry(lib, 'ps_maxpool_bwd', dy.dtype)(dx.data_ptr(), dy.data_ptr(), arg.data_ptr(),
                            Nb, H, W, C, P, Q, k, k, stride, pad,
                            current_stream_ptr())
         return dx, None, None, None
@@ -62,7 +68,7 @@ class _GlobalAvgPoolFn(torch.autograd.Function):
         x = x.contiguous(memory_format=_CL)
         Nb, C, H, W = x.shape
         y = torch.empty((Nb, C), dtype=x.dtype, device=x.device)
-        lib.ps_gavgpool_fwd(y.data_ptr(), x.data_ptr(), Nb, H * W, C,
+        _entry(lib, 'ps_gavgpool_fwd', x.dtype)(y.data_ptr(), x.data_ptr(), Nb, H * W, C,
                             current_stream_ptr())
         ctx.conf = (Nb, C, H, W)
         return y
@@ -74,7 +80,7 @@ class _GlobalAvgPoolFn(torch.autograd.Function):
         dy = dy.contiguous()
         dx = torch.empty((Nb, C, H, W), dtype=dy.dtype, device=dy.device,
                          memory_format=_CL)
-        lib.ps_gavgpool_bwd(dx.data_ptr(), dy.data_ptr(), Nb, H * W, C,
+        _entry(lib, 'ps_gavgpool_bwd', dy.dtype)(dx.data_ptr(), dy.data_ptr(), Nb, H * W, C,
                             current_stream_ptr())
         return dx
 
