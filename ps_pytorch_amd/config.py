@@ -97,6 +97,12 @@ def add_fit_args(parser: argparse.ArgumentParser) -> argparse.ArgumentParser:
                              'allreduce (collective DP on all N ranks — the '
                              'reference\'s vendored data_parallel_dist.py, built '
                              'properly)')
+    parser.add_argument('--loader', type=str, default='torch',
+                        help='torch | fused : real-data batch pipeline (torch '
+                             '= tensor-op augmentation with a CPU generator; '
+                             'fused = one in-tree kernel per batch with '
+                             'counter-based Philox draws, capturable into the '
+                             'step graph; synthetic data ignores it)')
     return parser
 
 
@@ -136,8 +142,11 @@ class JobConfig:
     engine: str = 'ps'
     optimizer: str = 'sgd'
     resume_step: int = 0
+    loader: str = 'torch'
 
     def __post_init__(self) -> None:
+        if self.loader not in ('torch', 'fused'):
+            raise ValueError(f"unknown --loader {self.loader!r}")
         if self.mode not in ('normal', 'kill', 'timeout'):
             raise ValueError(f"unknown --mode {self.mode!r}")
         if self.aggregation not in ('collective', 'gather'):

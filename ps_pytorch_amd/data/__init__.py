@@ -25,7 +25,9 @@ def prepare_data(args_or_cfg, rank: int = 0, num_shards: int = 1,
     reference's transform stacks (GPU-side, data/real.py). Files are looked
     up under --data-dir / $PS_DATA_ROOT / ./<name>_data (the paths the
     reference's pre-download script used). ImageNet-syn and missing files
-    use the synthetic generator (data/synthetic.py)."""
+    use the synthetic generator (data/synthetic.py). cfg.loader == 'fused'
+    selects the one-kernel Philox loader for real data (the synthetic
+    fallback ignores it)."""
     cfg = args_or_cfg
     dataset = getattr(cfg, 'dataset', 'MNIST')
     root = dataset_root(dataset, getattr(cfg, 'data_dir', None))
@@ -43,6 +45,12 @@ def prepare_data(args_or_cfg, rank: int = 0, num_shards: int = 1,
     logger.info('%s: real data from %s', dataset, root)
     train = RealDataset(dataset, 'train', root, device=device, dtype=dtype)
     test = RealDataset(dataset, 'test', root, device=device, dtype=dtype)
+    if getattr(cfg, 'loader', 'torch') == 'fused':
+        # one seed for the job; the rank is the Philox stream
+        return (RealResidentLoader(train, bs, shuffle=True, seed=seed,
+                                   rng='philox', stream=rank),
+                RealResidentLoader(test, tbs, shuffle=False, drop_last=False,
+                                   augment=False, rng='philox', stream=rank))
     return (RealResidentLoader(train, bs, shuffle=True, seed=seed + rank),
             RealResidentLoader(test, tbs, shuffle=False, drop_last=False,
                                augment=False))

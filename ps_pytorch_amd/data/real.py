@@ -18,6 +18,12 @@ transform stack (util.py:36-47) — instead of per-sample PIL work on host
 CPUs feeding a multiprocessing loader (the reference's vendored
 my_data_loader.py). Zero H2D traffic per step; the only per-batch work is
 one gather and a fused normalize/cast.
+
+Two loader modes (RealResidentLoader rng=): 'torch', the tensor-op pipeline
+above with offsets from a CPU torch.Generator, and 'philox' (--loader
+fused), one in-tree kernel per batch (ops/kernels/augment.hip) with
+counter-based draws — no host work per step, so the loader can be captured
+into the training step's hipGraph.
 """
 from __future__ import annotations
 
@@ -239,19 +245,49 @@ class RealDataset:
 
 class RealResidentLoader:
     """ResidentLoader-compatible surface over a RealDataset: iteration yields
-    (data, target); next_batch() wraps epochs; train split augments."""
+    (data, target); next_batch() wraps epochs; train split augments.
+
+    rng='torch' (default) builds each batch from torch ops with offsets from
+    a CPU torch.Generator. rng='philox' produces it with one fused call
+    (ops/augment.py): crop offsets and flips are counter-based Philox draws,
+    a pure function of (seed, stream, step, batch slot), identical on CPU
+    and GPU, and the batch comes out channels-last. `stream` tells
+    data-parallel replicas apart under one seed: it enters the Philox
+    counter and offsets the shuffle seed, so rank r under (seed, stream=r)
+    visits the indices rng='torch' visits under seed + r. The step counter
+    is a plain attribute — `step`, an int64 device tensor when the dataset
+    is on a GPU, `host_step`, an int, on CPU — it counts the batches that
+    drew random numbers."""
 
     def __init__(self, ds: RealDataset, batch_size: int, shuffle: bool = True,
-                 seed: int = 1, drop_last: bool = True, augment: bool = True):
+                 seed: int = 1, drop_last: bool = True, augment: bool = True,
+                 rng: str = 'torch', stream: int = 0):
+        if rng not in ('torch', 'philox'):
+            raise ValueError(f"unknown loader rng {rng!r}")
         self.ds = ds
         self.batch_size = batch_size
         self.shuffle = shuffle
         self.drop_last = drop_last
         self.augment = augment and ds.split == 'train'
+        self.rng = rng
+        self.stream = int(stream)
         self._epoch = 0
         self._pos = 0
         self._seed = seed
+        self._perm_seed = seed
         self._gen = torch.Generator().manual_seed(seed * 40503 + 7)
+        if rng == 'philox':
+            from ..ops.augment import uses_rng
+            self._perm_seed = seed + self.stream
+            self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+            self._mean255 = ds.mean.reshape(-1).tolist()
+            self._inv_std255 = ds.inv_std.reshape(-1).tolist()
+            self._draws = self.augment and uses_rng(ds.pad, ds.hflip)
+            self.host_step = 0
+            self.step = (torch.zeros((), dtype=torch.int64,
+                                     device=ds.x_u8.device)
+                         if self._draws and ds.x_u8.is_cuda else None)
+            self._gidx = None
         self._perm = self._make_perm()
 
     @property
@@ -261,8 +297,50 @@ class RealResidentLoader:
     def _make_perm(self) -> torch.Tensor:
         if not self.shuffle:
             return torch.arange(len(self.ds), device=self.ds.x_u8.device)
-        g = torch.Generator().manual_seed(self._seed * 7919 + self._epoch)
+        g = torch.Generator().manual_seed(self._perm_seed * 7919 + self._epoch)
         return torch.randperm(len(self.ds), generator=g).to(self.ds.x_u8.device)
+
+    def _fused(self, idx: torch.Tensor, out=None, out_y=None):
+        """One fused gather + augment + normalize call on `idx`."""
+        from ..ops.augment import augment_batch
+        ds = self.ds
+        on_gpu = ds.x_u8.is_cuda
+        xb, yb = augment_batch(
+            ds.x_u8, ds.y, idx, self._mean255, self._inv_std255, pad=ds.pad,
+            pad_mode=ds.pad_mode, hflip=ds.hflip, augment=self.augment,
+            seed=self.seed, stream=self.stream,
+            step=self.step if on_gpu else self.host_step, dtype=ds.dtype,
+            out=out, out_y=out_y)
+        if self._draws and not on_gpu:
+            self.host_step += 1
+        return xb, yb
+
+    # -- hipGraph capture of the loader (trainer.enable_graph_loader) --
+
+    def bind_static(self) -> None:
+        """Allocate the static index buffer a captured fill_static reads."""
+        if self.rng != 'philox' or not self.ds.x_u8.is_cuda:
+            raise ValueError("graph capture needs an rng='philox' loader "
+                             "over a GPU-resident dataset")
+        if not self.drop_last or len(self) == 0:
+            raise ValueError("graph capture needs full batches "
+                             "(drop_last=True, batch_size <= dataset size)")
+        self._gidx = torch.zeros(self.batch_size, dtype=torch.int64,
+                                 device=self.ds.x_u8.device)
+
+    def fill_static(self, out: torch.Tensor, out_y: torch.Tensor) -> None:
+        """Launch the loader kernel from the static index buffer into
+        (out, out_y): the part of a step that gets captured."""
+        self._fused(self._gidx, out, out_y)
+
+    def stage_next(self) -> None:
+        """Host side of a replay: advance the position (reshuffling at an
+        epoch boundary) and copy the next batch's indices into the static
+        buffer, ordered on the current stream."""
+        i = self._advance()
+        self._gidx.copy_(
+            self._perm[i * self.batch_size:(i + 1) * self.batch_size],
+            non_blocking=True)
 
     def __len__(self) -> int:
         n = len(self.ds)
@@ -271,6 +349,8 @@ class RealResidentLoader:
 
     def _batch(self, i: int):
         idx = self._perm[i * self.batch_size:(i + 1) * self.batch_size]
+        if self.rng == 'philox':
+            return self._fused(idx)
         xb = self.ds.x_u8.index_select(0, idx)
         yb = self.ds.y.index_select(0, idx)
         if self.augment:
@@ -283,11 +363,14 @@ class RealResidentLoader:
         self._epoch += 1
         self._perm = self._make_perm()
 
-    def next_batch(self):
+    def _advance(self) -> int:
         if self._pos >= len(self):
             self._pos = 0
             self._epoch += 1
             self._perm = self._make_perm()
         i = self._pos
         self._pos += 1
-        return self._batch(i)
+        return i
+
+    def next_batch(self):
+        return self._batch(self._advance())

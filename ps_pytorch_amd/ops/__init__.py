@@ -104,6 +104,13 @@ def _try_load() -> None:
         lib.ps_act_drop_bwd.argtypes = [ctypes.c_void_p] * 3 + [
             ctypes.c_long, ctypes.c_int, ctypes.c_float, ctypes.c_void_p]
         lib.ps_rng_advance.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        # out, out_y, x_u8, y, idx, B, C, H, W, dtype, pad, reflect, hflip,
+        # mean255 (host), inv_std255 (host), seed, stream, step_ptr, stream
+        lib.ps_augment_batch.argtypes = [ctypes.c_void_p] * 5 + [
+            ctypes.c_long] + [ctypes.c_int] * 7 + [
+            ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
+            ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p,
+            ctypes.c_void_p]
         # f32 family (conv_f32.hip + the f32 twins in pool / softmaxce)
         lib.ps_conv_fwd_f32.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int] * 11 + [ctypes.c_void_p]
         lib.ps_conv_dgrad_f32.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int] * 11 + [ctypes.c_void_p]

@@ -317,3 +317,77 @@ def pack_mask_bits(bits: torch.Tensor) -> torch.Tensor:
     import numpy as np
     b = bits.reshape(-1).cpu().numpy()
     return torch.from_numpy(np.packbits(b, bitorder='little'))
+
+
+# ---- fused augmentation loader (CPU oracle for ops/kernels/augment.hip) ----
+# Per batch slot b one Philox block: counter (b, 0, lo32(step),
+# (stream << 16) | 0xDA7A), key (lo32(seed), hi32(seed));
+# oy = (w0 * (2p+1)) >> 32, ox = (w1 * (2p+1)) >> 32, flip = hflip & (w2 >> 31).
+
+AUGMENT_SALT = 0xDA7A
+
+
+def augment_draws(B: int, pad: int, hflip: bool, seed: int, stream: int = 0,
+                  step: int = 0):
+    """(oy, ox, flip) of the B batch slots: int64 [B], int64 [B], bool [B];
+    offsets are uniform on 0..2*pad, flip is a fair coin (False without
+    hflip)."""
+    import numpy as np
+    ctr = np.zeros((B, 4), dtype=np.uint64)
+    ctr[:, 0] = np.arange(B, dtype=np.uint64)
+    ctr[:, 2] = int(step) & _U32
+    ctr[:, 3] = dropout_salt_stream(AUGMENT_SALT, stream)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    w = philox4x32_10(ctr, [seed & _U32, seed >> 32]).astype(np.uint64)
+    span = np.uint64(2 * int(pad) + 1)
+    oy = ((w[:, 0] * span) >> np.uint64(32)).astype(np.int64)
+    ox = ((w[:, 1] * span) >> np.uint64(32)).astype(np.int64)
+    flip = (w[:, 2] >> np.uint64(31)).astype(bool) & bool(hflip)
+    return torch.from_numpy(oy), torch.from_numpy(ox), torch.from_numpy(flip)
+
+
+def _augment_src(o, flip, L: int, pad: int, reflect: bool):
+    """Source coordinate [B, L] along one axis and its in-range mask."""
+    ar = torch.arange(L, device=o.device).view(1, L)
+    if flip is not None:
+        ar = torch.where(flip.view(-1, 1), L - 1 - ar, ar)
+    s = o.view(-1, 1) + ar - pad
+    if reflect:
+        s = torch.where(s < 0, -s, s)
+        s = torch.where(s >= L, 2 * (L - 1) - s, s)
+        return s, torch.ones_like(s, dtype=torch.bool)
+    ok = (s >= 0) & (s < L)
+    return s.clamp(0, L - 1), ok
+
+
+def augment_ref(x_u8: torch.Tensor, y: torch.Tensor, idx: torch.Tensor,
+                mean255, inv_std255, pad: int = 0, pad_mode=None,
+                hflip: bool = False, draws=None,
+                dtype: torch.dtype = torch.float32):
+    """Reference of the augment kernel in index arithmetic: output pixel
+    (b, h, w) reads source (oy + h - pad, ox + w' - pad), w' = W-1-w where
+    flipped, reflected back into the image (pad_mode 'reflect') or replaced
+    by uint8 0 ('constant'), then T((float(u8) - mean255[c]) * inv_std255[c])
+    with both operations rounded to f32. `draws` = (oy, ox, flip) from
+    augment_draws, or None for a plain gather + normalize. Returns the
+    [B,C,H,W] batch in channels-last memory and the labels."""
+    dev = x_u8.device
+    B = idx.numel()
+    _, C, H, W = x_u8.shape
+    if draws is None:
+        pad = 0
+        oy = ox = torch.zeros(B, dtype=torch.int64, device=dev)
+        flip = None
+    else:
+        oy, ox, flip = (t.to(dev) for t in draws)
+    sy, oky = _augment_src(oy, None, H, pad, pad_mode == 'reflect')
+    sx, okx = _augment_src(ox, flip, W, pad, pad_mode == 'reflect')
+    idx = idx.to(dev)
+    # advanced indices split by the channel slice -> [B, H, W, C]
+    u = x_u8[idx.view(B, 1, 1), :, sy.view(B, H, 1), sx.view(B, 1, W)].float()
+    ok = oky.view(B, H, 1, 1) & okx.view(B, 1, W, 1)
+    u = torch.where(ok, u, torch.zeros((), device=dev))
+    mean = torch.as_tensor(mean255, dtype=torch.float32, device=dev).view(C)
+    inv = torch.as_tensor(inv_std255, dtype=torch.float32, device=dev).view(C)
+    out = ((u - mean) * inv).to(dtype)
+    return out.permute(0, 3, 1, 2), y.index_select(0, idx)

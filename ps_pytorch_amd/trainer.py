@@ -124,6 +124,9 @@ class NNTrainer:
         tensor — read it only when needed to avoid a sync per step."""
         self._gx.copy_(data, non_blocking=True)
         self._gy.copy_(target, non_blocking=True)
+        return self._replay()
+
+    def _replay(self) -> torch.Tensor:
         self._graph.replay()
         # host-side BN batch counters don't tick during replay (host code
         # doesn't run); keep them canonical here
@@ -133,6 +136,54 @@ class NNTrainer:
                 m._nbt_host = getattr(m, '_nbt_host', 0) + 1
         self.cur_step += 1
         return self._gloss
+
+    # ---- captured step INCLUDING the data loader (real data) ----
+    # An rng='philox' RealResidentLoader produces a batch with one kernel
+    # whose randomness is a device-side counter, so loader + step capture as
+    # one graph: loader kernel -> static (_gx, _gy) -> _step_body. Per replay
+    # the host only copies the next B dataset indices into the loader's
+    # static index buffer (D2D, ordered on the stream). The 3 warmup steps
+    # consume real batches, so `enable_graph_loader` + k `graph_loader_step`s
+    # see the batch sequence of 3 + k eager next_batch()/train_step() calls.
+
+    def enable_graph_loader(self, loader) -> bool:
+        if self.device.type != 'cuda':
+            return False
+        ds = loader.dataset
+        if ds.dtype != self.compute_dtype:
+            raise ValueError(f"loader yields {ds.dtype}, the trainer computes "
+                             f"in {self.compute_dtype}")
+        loader.bind_static()             # raises unless a GPU philox loader
+        try:
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                for _ in range(3):     # warmup allocs/algos outside capture
+                    self._step_body(*loader.next_batch())
+                    self.cur_step += 1
+            torch.cuda.current_stream().wait_stream(side)
+            B = loader.batch_size
+            self._gx = torch.empty((B,) + tuple(ds.shape), dtype=ds.dtype,
+                                   device=self.device,
+                                   memory_format=torch.channels_last)
+            self._gy = torch.empty(B, dtype=torch.int64, device=self.device)
+            self._graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self._graph):
+                loader.fill_static(self._gx, self._gy)
+                self._gloss = self._step_body(self._gx, self._gy)
+            self._gloader = loader
+            return True
+        except Exception as e:   # pragma: no cover - depends on runtime
+            import warnings
+            warnings.warn(f"hipGraph capture failed, staying eager: {e}")
+            self._graph = None
+            return False
+
+    def graph_loader_step(self) -> torch.Tensor:
+        """Replay the captured loader + step on the loader's next batch;
+        returns the (device) loss tensor, as graph_step does."""
+        self._gloader.stage_next()
+        return self._replay()
 
     def train_and_validate(self, train_loader, test_loader,
                            max_steps: Optional[int] = None) -> None:
