@@ -82,6 +82,18 @@ def add_fit_args(parser: argparse.ArgumentParser) -> argparse.ArgumentParser:
     parser.add_argument('--aggregation', type=str, default='collective',
                         help='collective (reduce-to-root) | gather (per-worker P2P, '
                              'enables arrival-order --num-aggregate selection)')
+    parser.add_argument('--error-feedback', type=str2bool, nargs='?',
+                        const=True, default=False,
+                        help='error feedback for the lossy gradient wire '
+                             'codecs (gather+compress int8, or an fp32 '
+                             'gradient on a bf16 wire): each worker keeps '
+                             'what the codec dropped and adds it to its next '
+                             'gradient. The residual is worker-local and not '
+                             'checkpointed: --resume-step restarts it from '
+                             'zero, like the momentum buffer. With '
+                             '--num-aggregate below the worker count a late '
+                             'payload the PS discards is still charged to '
+                             'its worker\'s residual')
     parser.add_argument('--resume-step', type=int, default=0,
                         help='warm-start: load train-dir/model_step_<K> '
                              'into the global model before training '
@@ -143,6 +155,7 @@ class JobConfig:
     optimizer: str = 'sgd'
     resume_step: int = 0
     loader: str = 'torch'
+    error_feedback: bool = False
 
     def __post_init__(self) -> None:
         if self.loader not in ('torch', 'fused'):
@@ -165,6 +178,23 @@ class JobConfig:
                           "(arrival-order first-k drives the kill verdict); "
                           "switching aggregation to 'gather'")
             self.aggregation = 'gather'
+        # Error feedback only has something to feed back where the push
+        # loses bits: the int8 codec (gather + compress) or a bf16 wire under
+        # an fp32 gradient. A lossless wire gets the same normalize-and-warn
+        # treatment; the transport re-checks per rank with the actual dtypes
+        # (the bf16 wire only exists on GPUs).
+        if self.error_feedback and not (self.compress
+                                        or self.wire_dtype == 'bf16'):
+            import warnings
+            warnings.warn("--error-feedback has nothing to feed back on a "
+                          "lossless fp32 gradient wire (--compress-grad None "
+                          "--wire-dtype fp32); running without it")
+            self.error_feedback = False
+        if self.error_feedback and self.engine != 'ps':
+            import warnings
+            warnings.warn("--error-feedback applies to the PS engine's "
+                          "gradient push only; running without it")
+            self.error_feedback = False
 
     @property
     def compress(self) -> bool:

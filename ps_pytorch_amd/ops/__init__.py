@@ -57,6 +57,13 @@ def _try_load() -> None:
                                        ctypes.c_long, ctypes.c_void_p]
         lib.ps_pack_q8.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
                                    ctypes.c_long, ctypes.c_int, ctypes.c_void_p]
+        # error-feedback packs: the f32 residual rides after src
+        lib.ps_pack_q8_ef.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
+                                      ctypes.c_void_p, ctypes.c_long,
+                                      ctypes.c_int, ctypes.c_void_p]
+        lib.ps_pack_bf16_ef.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
+                                        ctypes.c_void_p, ctypes.c_long,
+                                        ctypes.c_void_p]
         lib.ps_unpack_q8.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
                                      ctypes.c_long, ctypes.c_int, ctypes.c_void_p]
         lib.ps_acc.argtypes = [ctypes.c_void_p, ctypes.c_void_p,

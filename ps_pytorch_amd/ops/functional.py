@@ -163,19 +163,91 @@ def pack_q8(payload: torch.Tensor, src: torch.Tensor) -> None:
         require_lib().ps_pack_q8(payload.data_ptr(), src.data_ptr(), n,
                                  dtype_tag(src.dtype), current_stream_ptr())
         return
+    q, scale = _q8_encode_cpu(src.to(torch.float32))
+    payload[:n] = q.view(-1)[:n].to(torch.int8).view(torch.uint8)
+    payload[qb:qb + 4 * scale.numel()].view(torch.float32).copy_(scale)
+
+
+def _q8_encode_cpu(x: torch.Tensor):
+    """CPU block encode of flat f32 `x`: (f32 quants [nblk, 256] holding the
+    clamped integers, zero in the pad; f32 scales [nblk])."""
+    n = x.numel()
     nblk = (n + Q8_BLOCK - 1) // Q8_BLOCK
-    x = torch.zeros(nblk * Q8_BLOCK, dtype=torch.float32)
-    x[:n] = src.to(torch.float32)
-    xb = x.view(nblk, Q8_BLOCK)
+    xp = torch.zeros(nblk * Q8_BLOCK, dtype=torch.float32)
+    xp[:n] = x
+    xb = xp.view(nblk, Q8_BLOCK)
     m = xb.abs().amax(dim=1)
     # NB: divide f32-tensor by f32-tensor — torch computes python-scalar /
     # tensor in f64 and casts, which is 1 ulp off strict f32 division and
     # breaks bitwise parity with the GPU kernel's IEEE f32 divide.
     c127 = torch.full_like(m, 127.0)
     inv = torch.where(m > 0, c127 / m, torch.zeros_like(m))
-    q = torch.clamp(torch.round(xb * inv[:, None]), -127, 127).to(torch.int8)
-    payload[:n] = q.view(-1)[:n].view(torch.uint8)
-    payload[qb:qb + 4 * nblk].view(torch.float32).copy_(m / c127)
+    q = torch.clamp(torch.round(xb * inv[:, None]), -127, 127)
+    return q, m / c127
+
+
+def _check_residual(residual: torch.Tensor, src: torch.Tensor) -> None:
+    if residual.dtype != torch.float32:
+        raise TypeError("error-feedback residual must be f32")
+    _check_flat(residual, "residual", src.numel())
+    if residual.device != src.device:
+        raise ValueError("residual and src must live on the same device")
+
+
+def pack_q8_ef(payload: torch.Tensor, src: torch.Tensor,
+               residual: torch.Tensor) -> None:
+    """pack_q8 with error feedback: encode c = src + residual and leave
+    c - decode(payload) in `residual` (f32, same numel as src, in place) —
+    what this step's code could not carry is added to the next step's
+    gradient. With residual == 0 the payload equals pack_q8's.
+
+    Per element, each operation rounded to f32 once: c = g + e; per block
+    m = max|c|, inv = 127/m (0 when m == 0), scale = m/127;
+    q = clamp(rint(c*inv), +-127); dec = q*scale; e' = c - dec. dec is what
+    unpack_q8 (no accumulate) yields. The CPU path below is the bitwise
+    reference of ps_pack_q8_ef."""
+    n = src.numel()
+    qb, tot = q8_layout(n)
+    if payload.dtype != torch.uint8 or payload.numel() != tot:
+        raise ValueError(f"payload must be uint8[{tot}], got "
+                         f"{payload.dtype}[{payload.numel()}]")
+    if src.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError("q8 source must be f32 or bf16")
+    _check_flat(src, "src", n)
+    _check_residual(residual, src)
+    if src.is_cuda:
+        require_lib().ps_pack_q8_ef(payload.data_ptr(), src.data_ptr(),
+                                    residual.data_ptr(), n,
+                                    dtype_tag(src.dtype), current_stream_ptr())
+        return
+    c = src.to(torch.float32) + residual
+    q, scale = _q8_encode_cpu(c)
+    payload[:n] = q.view(-1)[:n].to(torch.int8).view(torch.uint8)
+    payload[qb:qb + 4 * scale.numel()].view(torch.float32).copy_(scale)
+    dec = q * scale[:, None]
+    residual.copy_(c - dec.view(-1)[:n])
+
+
+def pack_wire_ef(dst: torch.Tensor, src: torch.Tensor,
+                 residual: torch.Tensor) -> None:
+    """f32 -> bf16 wire pack with error feedback: dst = bf16(src + residual)
+    (round to nearest even) and residual = (src + residual) - f32(dst), in
+    place; the subtraction is exact in f32."""
+    n = src.numel()
+    if src.dtype != torch.float32 or dst.dtype != torch.bfloat16:
+        raise TypeError(f"error-feedback wire pack is f32 -> bf16, got "
+                        f"{src.dtype} -> {dst.dtype}")
+    _check_flat(src, "src", n)
+    _check_flat(dst, "dst", n)
+    _check_residual(residual, src)
+    if src.is_cuda:
+        require_lib().ps_pack_bf16_ef(dst.data_ptr(), src.data_ptr(),
+                                      residual.data_ptr(), n,
+                                      current_stream_ptr())
+        return
+    c = src + residual
+    dst.copy_(c.to(torch.bfloat16))
+    residual.copy_(c - dst.to(torch.float32))
 
 
 def unpack_q8(dst: torch.Tensor, payload: torch.Tensor,

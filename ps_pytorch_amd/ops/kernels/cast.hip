@@ -26,6 +26,32 @@ __global__ __launch_bounds__(256) void pack_bf16_kernel(
         for (long i = nvec << 2; i < n; ++i) dst[i] = f32_to_bf16(src[i]);
 }
 
+// Error-feedback pack: w = bf16(g + e), e' = (g + e) - f32(w). The
+// subtraction is exact in f32 (w is c rounded to 8 significant bits), so
+// c = g + e is the only rounding the feedback loop adds. residual is f32[n],
+// updated in place, and aliases neither src nor dst.
+__global__ __launch_bounds__(256) void pack_bf16_ef_kernel(
+    unsigned short* __restrict__ dst, const float* __restrict__ src,
+    float* __restrict__ residual, long n)
+{
+    EW_IDX
+    long nvec = n >> 2;
+    for (long i = gid; i < nvec; i += stride) {
+        float4_t c = ((const float4_t*)src)[i] + ((const float4_t*)residual)[i];
+        ushort4_t o = {f32_to_bf16(c.x), f32_to_bf16(c.y), f32_to_bf16(c.z), f32_to_bf16(c.w)};
+        float4_t d = {bf16_to_f32(o.x), bf16_to_f32(o.y), bf16_to_f32(o.z), bf16_to_f32(o.w)};
+        ((unsigned long long*)dst)[i] = *(unsigned long long*)&o;
+        ((float4_t*)residual)[i] = c - d;
+    }
+    if (gid == 0)
+        for (long i = nvec << 2; i < n; ++i) {
+            float c = src[i] + residual[i];
+            unsigned short w = f32_to_bf16(c);
+            dst[i] = w;
+            residual[i] = c - bf16_to_f32(w);
+        }
+}
+
 __global__ __launch_bounds__(256) void unpack_bf16_kernel(
     float* __restrict__ dst, const unsigned short* __restrict__ src, long n)
 {
@@ -44,6 +70,13 @@ extern "C" void ps_pack_bf16(void* dst, const void* src, long n, void* stream) {
     int blocks; ew_grid(n / 4, 256, &blocks);
     hipLaunchKernelGGL(pack_bf16_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
                        (unsigned short*)dst, (const float*)src, n);
+}
+
+extern "C" void ps_pack_bf16_ef(void* dst, const void* src, void* residual,
+                                long n, void* stream) {
+    int blocks; ew_grid(n / 4, 256, &blocks);
+    hipLaunchKernelGGL(pack_bf16_ef_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
+                       (unsigned short*)dst, (const float*)src, (float*)residual, n);
 }
 
 extern "C" void ps_unpack_bf16(void* dst, const void* src, long n, void* stream) {

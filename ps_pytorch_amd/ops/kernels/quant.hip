@@ -77,6 +77,82 @@ __global__ __launch_bounds__(256) void pack_q8_kernel(
     }
 }
 
+// Error-feedback pack: encode c = g + e instead of g and keep what the code
+// could not represent, e' = c - decode(code), in the worker's f32 residual
+// for the next step (EF-SGD / 1-bit SGD). Same payload layout and wave
+// mapping as pack_q8_kernel; costs one extra f32 read + write per element.
+//
+// c = g + e is the only inexact step of the feedback loop; dec = q * scale
+// is rounded to f32 exactly as unpack_q8 (no accumulate) rounds it, and
+// e' = c - dec is a separate subtraction. Contraction is switched off so
+// the two never fuse into an fma — that is what keeps the torch CPU path in
+// ops/functional.py a bitwise oracle.
+template <bool BF16>
+__global__ __launch_bounds__(256) void pack_q8_ef_kernel(
+    char* __restrict__ q, float* __restrict__ scales,
+    const void* __restrict__ src_, float* __restrict__ residual,
+    long n, long nblk)
+{
+#pragma clang fp contract(off)
+    const float* __restrict__ srcf = (const float*)src_;
+    const unsigned short* __restrict__ srcb = (const unsigned short*)src_;
+    long blk = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    long stride = (long)gridDim.x * 4;
+    for (; blk < nblk; blk += stride) {
+        int lane = threadIdx.x & 63;
+        long idx = blk * Q8_BLOCK + (long)lane * 4;
+        bool full = idx + 4 <= n;
+        float c[4];
+        if (full) {
+            float4_t e = *(const float4_t*)(residual + idx);
+            if constexpr (BF16) {
+                unsigned long long u = *(const unsigned long long*)(srcb + idx);
+                ushort4_t s = *(ushort4_t*)&u;
+                c[0] = bf16_to_f32(s.x) + e.x; c[1] = bf16_to_f32(s.y) + e.y;
+                c[2] = bf16_to_f32(s.z) + e.z; c[3] = bf16_to_f32(s.w) + e.w;
+            } else {
+                float4_t x = *(const float4_t*)(srcf + idx);
+                c[0] = x.x + e.x; c[1] = x.y + e.y;
+                c[2] = x.z + e.z; c[3] = x.w + e.w;
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                c[k] = (idx + k < n)
+                    ? (BF16 ? bf16_to_f32(srcb[idx + k]) : srcf[idx + k])
+                          + residual[idx + k]
+                    : 0.f;
+        }
+        float m = 0.f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) m = fmaxf(m, fabsf(c[k]));
+#pragma unroll
+        for (int off = 32; off; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+        float inv = m > 0.f ? 127.f / m : 0.f;
+        float scale = m / 127.f;
+        if (lane == 0) scales[blk] = scale;
+        char4_t o;
+        float4_t en;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float r = rintf(c[k] * inv);
+            r = fminf(127.f, fmaxf(-127.f, r));
+            o[k] = (char)r;
+            float dec = r * scale;
+            en[k] = c[k] - dec;
+        }
+        if (full) {
+            *(char4_t*)(q + idx) = o;
+            *(float4_t*)(residual + idx) = en;
+        } else {
+            for (int k = 0; k < 4 && idx + k < n; ++k) {
+                q[idx + k] = o[k];
+                residual[idx + k] = en[k];
+            }
+        }
+    }
+}
+
 template <bool ACC>
 __global__ __launch_bounds__(256) void unpack_q8_kernel(
     float* __restrict__ dst, const char* __restrict__ q,
@@ -150,6 +226,24 @@ extern "C" void ps_pack_q8(void* payload, const void* src, long n, int src_dtype
     else
         hipLaunchKernelGGL(pack_q8_kernel<false>, dim3(blocks), dim3(256), 0,
                            (hipStream_t)stream, q, scales, src, n, nblk);
+}
+
+// residual: f32[n], 16-B aligned (a bucket slice), read and rewritten in
+// place; it must not alias src or payload.
+extern "C" void ps_pack_q8_ef(void* payload, const void* src, void* residual,
+                              long n, int src_dtype, void* stream) {
+    long nblk = q8_nblk(n);
+    char* q = (char*)payload;
+    float* scales = (float*)(q + q8_qbytes(n));
+    int blocks; ew_grid(nblk * 64, 256, &blocks);
+    if (src_dtype == PS_BF16)
+        hipLaunchKernelGGL(pack_q8_ef_kernel<true>, dim3(blocks), dim3(256), 0,
+                           (hipStream_t)stream, q, scales, src,
+                           (float*)residual, n, nblk);
+    else
+        hipLaunchKernelGGL(pack_q8_ef_kernel<false>, dim3(blocks), dim3(256), 0,
+                           (hipStream_t)stream, q, scales, src,
+                           (float*)residual, n, nblk);
 }
 
 extern "C" void ps_unpack_q8(void* dst, const void* payload, long n, int accumulate,

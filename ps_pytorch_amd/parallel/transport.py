@@ -19,6 +19,9 @@ bucketed collectives on ONE flat buffer over `torch.distributed`
   compression                    -> gather mode sends block-scaled int8
         payloads (ops/kernels/quant.hip, 4x smaller than f32) — the GPU
         re-expression of blosc g_compress (ref compression.py:18-46).
+        Both wire codecs (int8, and bf16 under an f32 gradient) are lossy
+        where blosc was not; --error-feedback keeps each worker's rounding
+        error in a local f32 residual and re-injects it next step.
   kill (tag 77) / control        -> gloo side-channel (ControlPlane below):
         RCCL collectives cannot be probed or cancelled, so the straggler
         kill signal travels host-side while payload matching stays intact
@@ -82,7 +85,8 @@ class PSTransport:
                  device: torch.device, rank: int, world: int,
                  group: Optional[dist.ProcessGroup] = None,
                  mode: str = 'collective', compress: bool = False,
-                 comm_type: str = 'Bcast', track_killed: bool = False):
+                 comm_type: str = 'Bcast', track_killed: bool = False,
+                 error_feedback: bool = False):
         if mode not in ('collective', 'gather'):
             raise ValueError(f"unknown aggregation mode {mode!r}")
         self.comm_type = comm_type
@@ -101,6 +105,32 @@ class PSTransport:
         n = flat.padded
         self.wire_w = torch.zeros(n, dtype=wire_dtype, device=device)
         self.wire_g = torch.zeros(n, dtype=wire_dtype, device=device)
+        # Error feedback (worker ranks only; the payload format and the PS
+        # are unchanged): where the push loses bits — the q8 codec, or an
+        # f32 gradient packed to a bf16 wire — the worker keeps what the
+        # codec dropped in an f32 residual and adds it to the next step's
+        # gradient before encoding. Bucket bounds are multiples of 8
+        # elements (flat.py), so every residual[b.start:b.end] slice is
+        # 16-B aligned for the vector kernels. Worker-local, never
+        # checkpointed. Known limit: with --num-aggregate below the worker
+        # count the PS may discard a late payload whose residual this worker
+        # has already charged — the worker cannot see that.
+        self.ef_active = False
+        if error_feedback and rank != PS_RANK:
+            lossy = self.compress or (
+                wire_dtype == torch.bfloat16
+                and flat.flat_g.dtype != wire_dtype)
+            if lossy:
+                self.ef_active = True
+                self.residual = torch.zeros(n, dtype=torch.float32,
+                                            device=device)
+            else:
+                import warnings
+                warnings.warn(
+                    f"--error-feedback: the gradient push is lossless here "
+                    f"({flat.flat_g.dtype} gradients on a {wire_dtype} wire, "
+                    f"{mode} mode, compress={self.compress}); running "
+                    f"without it")
         self._works: List[dist.Work] = []
         self._bcast_works: List[dist.Work] = []
         # program-order matching guard: NCCL IGNORES P2P tags — matching of
@@ -267,7 +297,10 @@ class PSTransport:
         collective: pack to wire dtype, ncclReduce(sum) to rank 0.
         gather:     pack (q8 or wire dtype), ncclSend to rank 0.
         killed=True sends a zero payload without touching the grads (the
-        straggler-abort path: matching stays intact, compute is skipped)."""
+        straggler-abort path: matching stays intact, compute is skipped) —
+        nor the error-feedback residual: nothing was computed, so nothing
+        is owed. Buckets really pushed before a mid-backward abort keep
+        their updated residual."""
         # NCCL ignores tags: matching is per-pair FIFO, so bucket order is
         # the protocol. Enforce it (reset in wait_all at step end).
         assert b.index == self._next_push, (
@@ -280,7 +313,7 @@ class PSTransport:
             if killed:
                 wire.zero_()
             elif wire.dtype != src.dtype:
-                ops_f.pack_wire(wire, src)
+                self._pack_wire(wire, src, b)
             else:
                 wire.copy_(src)
             w = dist.reduce(wire, dst=PS_RANK, op=dist.ReduceOp.SUM,
@@ -290,7 +323,11 @@ class PSTransport:
                 payload = self._zero_payload[:self._pl_off[b.index][1]]
             else:
                 payload = self._worker_payload_slice(b)
-                ops_f.pack_q8(payload, self.flat.grad_slice(b))
+                if self.ef_active:
+                    ops_f.pack_q8_ef(payload, self.flat.grad_slice(b),
+                                     self.residual[b.start:b.end])
+                else:
+                    ops_f.pack_q8(payload, self.flat.grad_slice(b))
             w = dist.isend(payload, dst=PS_RANK, group=self.group, tag=b.index)
         else:
             if killed:
@@ -299,12 +336,21 @@ class PSTransport:
                 src = self.flat.grad_slice(b)
                 wire = self.grad_wire_slice(b)
                 if wire.dtype != src.dtype:
-                    ops_f.pack_wire(wire, src)
+                    self._pack_wire(wire, src, b)
                 else:
                     wire.copy_(src)
             w = dist.isend(wire, dst=PS_RANK, group=self.group, tag=b.index)
         self._works.append(w)
         return w
+
+    def _pack_wire(self, wire: torch.Tensor, src: torch.Tensor,
+                   b: Bucket) -> None:
+        """Cast one bucket to the wire dtype, through the residual when
+        error feedback is active (ef_active implies f32 -> bf16 here)."""
+        if self.ef_active:
+            ops_f.pack_wire_ef(wire, src, self.residual[b.start:b.end])
+        else:
+            ops_f.pack_wire(wire, src)
 
     def _worker_payload_slice(self, b: Bucket) -> torch.Tensor:
         off, nbytes = self._pl_off[b.index]

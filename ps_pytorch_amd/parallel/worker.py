@@ -76,7 +76,8 @@ class DistributedWorker:
                                      compress=cfg.compress,
                                      comm_type=cfg.comm_type,
                                      track_killed=(cfg.mode == 'timeout'
-                                                   and cfg.aggregation == 'gather'))
+                                                   and cfg.aggregation == 'gather'),
+                                     error_feedback=cfg.error_feedback)
         # straggler handling (ref resnet_split.py:503-728): 'kill' polls the
         # PS's gloo signal from backward hooks; 'timeout' aborts locally past
         # --kill-threshold seconds. Both raise StepKilled mid-backward and
