@@ -115,6 +115,14 @@ def add_fit_args(parser: argparse.ArgumentParser) -> argparse.ArgumentParser:
                              'fused = one in-tree kernel per batch with '
                              'counter-based Philox draws, capturable into the '
                              'step graph; synthetic data ignores it)')
+    parser.add_argument('--train-metrics', type=str2bool, nargs='?',
+                        const=True, default=False,
+                        help='Prec@1 / Prec@5 of the training batches on the '
+                             'log lines (the reference trainer\'s step line, '
+                             'nn_ops.py:80-86): counted on the device by the '
+                             'fused loss kernel, inside the captured step, '
+                             'and read once per --log-interval; covers the '
+                             'steps since the last log line')
     return parser
 
 
@@ -156,6 +164,7 @@ class JobConfig:
     resume_step: int = 0
     loader: str = 'torch'
     error_feedback: bool = False
+    train_metrics: bool = False
 
     def __post_init__(self) -> None:
         if self.loader not in ('torch', 'fused'):

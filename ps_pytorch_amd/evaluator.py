@@ -11,14 +11,13 @@ import os
 import time
 
 import torch
-import torch.nn.functional as F
 
 from .config import JobConfig, add_fit_args, input_shape_of, num_classes_of
 from .data import prepare_data
 from .models import build_model
 from .utils.checkpoint import model_step_path
 from .utils.logging import get_logger
-from .utils.metrics import accuracy
+from .ops.metrics import MetricAccumulator
 
 logger = get_logger('ps_pytorch_amd.evaluator')
 
@@ -81,20 +80,15 @@ class DistributedEvaluator:
     def _evaluate_model(self, test_loader):
         self.network.eval()
         pdtype = next(self.network.parameters()).dtype
-        tot, loss_sum, p1_sum, p5_sum = 0, 0.0, 0.0, 0.0
+        # one device-side accumulator per evaluation: no host sync per batch,
+        # f32/f64 row math whatever the logits' dtype (ops/metrics.py)
+        acc = MetricAccumulator(self.device, ks=(1, 5))
         for data, target in test_loader:
             data = data.to(self.device, pdtype)   # loader dtype may differ
             target = target.to(self.device)
-            out = self.network(data)
-            loss_sum += float(F.cross_entropy(out, target, reduction='sum'))
-            k = min(5, out.shape[1])
-            p1, pk = accuracy(out, target, topk=(1, k))
-            bs = target.size(0)
-            p1_sum += float(p1) * bs
-            p5_sum += float(pk) * bs
-            tot += bs
-        return (loss_sum / max(tot, 1), p1_sum / max(tot, 1),
-                p5_sum / max(tot, 1))
+            acc.update(self.network(data), target)
+        res = acc.result()
+        return res.loss, res.prec[1], res.prec[5]
 
 
 def main(argv=None) -> None:

@@ -30,6 +30,7 @@ F32_SYMBOLS = (
     'ps_maxpool_fwd_f32', 'ps_maxpool_bwd_f32',
     'ps_gavgpool_fwd_f32', 'ps_gavgpool_bwd_f32',
     'ps_softmax_ce_fwd_f32', 'ps_softmax_ce_bwd_f32',
+    'ps_ce_metrics_f32', 'ps_softmax_ce_fwd_metrics_f32',
 )
 
 
@@ -89,6 +90,13 @@ def _try_load() -> None:
             ctypes.c_long, ctypes.c_int, ctypes.c_void_p]
         lib.ps_softmax_ce_bwd.argtypes = [ctypes.c_void_p] * 5 + [
             ctypes.c_long, ctypes.c_int, ctypes.c_void_p]
+        # fused loss + prec@k (metrics.hip). eval: state, row_ws, rank,
+        # logits, target, M, C, nk, k0..k3, stream; the training entry
+        # carries loss, lse in front (the ps_softmax_ce_fwd outputs)
+        lib.ps_ce_metrics.argtypes = [ctypes.c_void_p] * 5 + [
+            ctypes.c_long] + [ctypes.c_int] * 6 + [ctypes.c_void_p]
+        lib.ps_softmax_ce_fwd_metrics.argtypes = [ctypes.c_void_p] * 7 + [
+            ctypes.c_long] + [ctypes.c_int] * 6 + [ctypes.c_void_p]
         lib.ps_maxpool_fwd.argtypes = [ctypes.c_void_p] * 3 + [
             ctypes.c_int] * 10 + [ctypes.c_void_p]
         lib.ps_maxpool_bwd.argtypes = [ctypes.c_void_p] * 3 + [
@@ -126,6 +134,9 @@ def _try_load() -> None:
             ctypes.c_long, ctypes.c_int, ctypes.c_void_p]
         lib.ps_softmax_ce_fwd_f32.argtypes = lib.ps_softmax_ce_fwd.argtypes
         lib.ps_softmax_ce_bwd_f32.argtypes = lib.ps_softmax_ce_bwd.argtypes
+        lib.ps_ce_metrics_f32.argtypes = lib.ps_ce_metrics.argtypes
+        lib.ps_softmax_ce_fwd_metrics_f32.argtypes = \
+            lib.ps_softmax_ce_fwd_metrics.argtypes
         lib.ps_maxpool_fwd_f32.argtypes = lib.ps_maxpool_fwd.argtypes
         lib.ps_maxpool_bwd_f32.argtypes = lib.ps_maxpool_bwd.argtypes
         lib.ps_gavgpool_fwd_f32.argtypes = lib.ps_gavgpool_fwd.argtypes

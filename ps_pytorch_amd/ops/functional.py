@@ -463,3 +463,52 @@ def augment_ref(x_u8: torch.Tensor, y: torch.Tensor, idx: torch.Tensor,
     inv = torch.as_tensor(inv_std255, dtype=torch.float32, device=dev).view(C)
     out = ((u - mean) * inv).to(dtype)
     return out.permute(0, 3, 1, 2), y.index_select(0, idx)
+
+
+# ---- fused loss + prec@k (CPU oracle for ops/kernels/metrics.hip) ----
+# rank(m) = #{c != t : x[c] > x[t] or isnan(x[c])} + #{c < t : x[c] == x[t]}:
+# ties go to the lower class index, so the count never depends on a sort's
+# tie order. Row m is a hit at k iff rank(m) < min(k, C); a NaN at the target
+# misses at every k; a row whose target is outside [0, C) is invalid — never
+# used as an index, worth 0 in the loss sum and in every hit count, and
+# counted on its own.
+
+METRIC_MAX_KS = 4
+
+
+def check_ks(ks) -> tuple:
+    ks = tuple(int(k) for k in ks)
+    if not 1 <= len(ks) <= METRIC_MAX_KS:
+        raise ValueError(f"between 1 and {METRIC_MAX_KS} values of k, "
+                         f"got {len(ks)}")
+    if any(k < 1 for k in ks):
+        raise ValueError(f"every k must be >= 1, got {ks}")
+    return ks
+
+
+def ce_topk_reference(logits: torch.Tensor, target: torch.Tensor,
+                      ks=(1, 5)):
+    """(loss_sum f64 [], hits i64 [len(ks)], rows i64 [], invalid i64 []) of
+    one [M, C] batch by the rule above, in plain torch on the logits' device
+    and without a host sync; the row loss is float64 log-sum-exp minus the
+    target logit. `rows` counts the valid rows."""
+    ks = check_ks(ks)
+    if logits.dim() != 2:
+        raise ValueError(f"logits must be [M, C], got {tuple(logits.shape)}")
+    x = logits.detach()
+    M, C = x.shape
+    t = target.detach().to(device=x.device, dtype=torch.int64).reshape(M)
+    valid = (t >= 0) & (t < C)
+    tc = t.clamp(0, max(C - 1, 0)).view(M, 1)
+    xt = x.gather(1, tc)
+    idx = torch.arange(C, device=x.device).view(1, C)
+    above = ((x > xt) | torch.isnan(x)) & (idx != tc)
+    tie = (x == xt) & (idx < tc)
+    rank = above.sum(1) + tie.sum(1)
+    rank = torch.where(torch.isnan(xt.view(M)), torch.full_like(rank, C), rank)
+    hits = torch.stack([((rank < min(k, C)) & valid).sum() for k in ks])
+    x64 = x.to(torch.float64)
+    row = torch.logsumexp(x64, dim=1) - xt.view(M).to(torch.float64)
+    loss_sum = torch.where(valid, row, torch.zeros_like(row)).sum()
+    rows = valid.sum()
+    return loss_sum, hits, rows, M - rows

@@ -20,13 +20,15 @@ import torch
 
 from ..ops.dropout import PsDropout
 from ..ops.loss import cross_entropy as ps_cross_entropy
+from ..ops.metrics import MetricAccumulator
 
 from ..config import JobConfig, input_shape_of, num_classes_of
 from ..models import build_model
 from ..parallel.flat import FlatSpace, prep_model
 from ..parallel.transport import ControlPlane, PSTransport, StepKilled
 from ..utils.checkpoint import save_model_step
-from ..utils.logging import get_logger, worker_log_line
+from ..utils.logging import (get_logger, worker_log_line,
+                             worker_metrics_line)
 
 logger = get_logger('ps_pytorch_amd.worker')
 
@@ -52,6 +54,10 @@ class DistributedWorker:
         self.network = None
         self.flat: Optional[FlatSpace] = None
         self.transport: Optional[PSTransport] = None
+        # --train-metrics: prec@k of this worker's batches, counted on the
+        # device by the loss kernel and read at log time
+        self.train_metrics = (MetricAccumulator(device, ks=(1, 5))
+                              if getattr(cfg, 'train_metrics', False) else None)
 
     # ---- setup ----
 
@@ -184,7 +190,8 @@ class DistributedWorker:
         try:
             t0 = time.time()
             out = self.network(data)
-            loss = ps_cross_entropy(out, target)
+            loss = ps_cross_entropy(out, target,
+                                    metrics=self.train_metrics)
             if hip_ev is not None:
                 hip_ev[1].record()
             self.f_dur = time.time() - t0
@@ -260,6 +267,12 @@ class DistributedWorker:
                         float('nan') if loss is None else float(loss),
                         time.time() - iter_start, fetch_dur, self.f_dur,
                         self.b_dur, comm_dur))
+                    if self.train_metrics is not None:
+                        # the steps since the last log line
+                        tm = self.train_metrics.result()
+                        self.train_metrics.reset()
+                        logger.info(worker_metrics_line(
+                            self.rank, self.cur_step, tm.prec[1], tm.prec[5]))
                 # checkpoint division of labor mirrors the reference
                 # (distributed_worker.py:175-177): rank 1 saves nets with BN
                 # buffers (ResNet/VGG) so running stats come from a worker.

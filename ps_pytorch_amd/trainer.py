@@ -14,7 +14,6 @@ from typing import Optional
 
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 
 from .ops.loss import cross_entropy as ps_cross_entropy
 
@@ -22,7 +21,7 @@ from .config import JobConfig, num_classes_of, input_shape_of
 from .models import build_model
 from .optim import FlatSGD, FlatAdam
 from .parallel.flat import FlatSpace, prep_model
-from .utils.metrics import accuracy
+from .ops.metrics import MetricAccumulator
 from .utils.logging import get_logger
 
 logger = get_logger('ps_pytorch_amd.trainer')
@@ -42,6 +41,10 @@ class NNTrainer:
         self.flat: Optional[FlatSpace] = None
         self.optimizer = None
         self.cur_step = 0
+        # --train-metrics: loss / prec@k of the training batches, summed on
+        # the device inside the step (captured with it) and read at log time
+        self.train_metrics = (MetricAccumulator(device, ks=(1, 5))
+                              if getattr(cfg, 'train_metrics', False) else None)
 
     def build_model(self, num_classes: Optional[int] = None) -> None:
         cfg = self.cfg
@@ -68,7 +71,17 @@ class NNTrainer:
 
     def _loss(self, data, target):
         out = self.network(data)
-        return ps_cross_entropy(out, target), out
+        return ps_cross_entropy(out, target, metrics=self.train_metrics), out
+
+    def read_train_metrics(self):
+        """Loss / prec@k of the training batches since the last read (one
+        host sync), then an asynchronous reset; None without
+        --train-metrics."""
+        if self.train_metrics is None:
+            return None
+        res = self.train_metrics.result()
+        self.train_metrics.reset()
+        return res
 
     def _step_body(self, data, target) -> torch.Tensor:
         self.flat.zero_grads()
@@ -107,6 +120,9 @@ class NNTrainer:
                 for _ in range(3):     # warmup allocs/algos outside capture
                     self._step_body(example_x, example_y)
             torch.cuda.current_stream().wait_stream(side)
+            if self.train_metrics is not None:
+                # the warmup steps above are not counted in cur_step
+                self.train_metrics.reset()
             self._gx = example_x.clone()
             self._gy = example_y.clone()
             self._graph = torch.cuda.CUDAGraph()
@@ -197,8 +213,13 @@ class NNTrainer:
                 target = target.to(self.device)
                 loss = self.train_step(data, target)
                 if self.cur_step % cfg.log_interval == 0:
-                    logger.info('Step: %d, Epoch: %d, Loss: %.4f, Time: %.4f',
-                                self.cur_step, epoch, loss, time.time() - t0)
+                    line = 'Step: %d, Epoch: %d, Loss: %.4f, Time: %.4f' % (
+                        self.cur_step, epoch, loss, time.time() - t0)
+                    tm = self.read_train_metrics()
+                    if tm is not None:   # the steps since the last log line
+                        line += ', Prec@1: %.2f, Prec@5: %.2f' % (
+                            tm.prec[1], tm.prec[5])
+                    logger.info(line)
                 if self.cur_step >= max_steps:
                     return
             self.validate(test_loader)
@@ -206,20 +227,13 @@ class NNTrainer:
     @torch.no_grad()
     def validate(self, test_loader) -> float:
         self.network.eval()
-        tot, p1_sum, p5_sum, loss_sum = 0, 0.0, 0.0, 0.0
+        acc = MetricAccumulator(self.device, ks=(1, 5))
         for data, target in test_loader:
             data = data.to(self.device, self.compute_dtype)
             target = target.to(self.device)
-            out = self.network(data)
-            loss_sum += float(F.cross_entropy(out.float(), target,
-                                              reduction='sum'))
-            k = min(5, out.shape[1])
-            p1, pk = accuracy(out.float(), target, topk=(1, k))
-            bs = target.size(0)
-            p1_sum += float(p1) * bs
-            p5_sum += float(pk) * bs
-            tot += bs
+            acc.update(self.network(data), target)
+        res = acc.result()     # the one host sync of the evaluation
         self.network.train()
         logger.info('Validation: loss %.4f, prec@1 %.2f, prec@5 %.2f',
-                    loss_sum / max(tot, 1), p1_sum / max(tot, 1), p5_sum / max(tot, 1))
-        return p1_sum / max(tot, 1)
+                    res.loss, res.prec[1], res.prec[5])
+        return res.prec[1]
