@@ -94,6 +94,18 @@ def add_fit_args(parser: argparse.ArgumentParser) -> argparse.ArgumentParser:
                              '--num-aggregate below the worker count a late '
                              'payload the PS discards is still charged to '
                              'its worker\'s residual')
+    parser.add_argument('--compress-codec', type=str, default='q8',
+                        help='q8 | topk : gather-mode gradient codec under '
+                             '--compress-grad compress. q8 = block-scaled '
+                             'int8 (4x under an fp32 wire); topk = the '
+                             '--topk-k largest magnitudes of every 256 '
+                             'elements as (u8 index, bf16 value), the rest '
+                             'carried in the error-feedback residual '
+                             '(switches --error-feedback on)')
+    parser.add_argument('--topk-k', type=int, default=16, metavar='K',
+                        help='4 | 8 | 16 | 32 : elements kept per 256-block '
+                             'by --compress-codec topk (3*K bytes per block '
+                             'on the wire)')
     parser.add_argument('--resume-step', type=int, default=0,
                         help='warm-start: load train-dir/model_step_<K> '
                              'into the global model before training '
@@ -165,8 +177,15 @@ class JobConfig:
     loader: str = 'torch'
     error_feedback: bool = False
     train_metrics: bool = False
+    compress_codec: str = 'q8'
+    topk_k: int = 16
 
     def __post_init__(self) -> None:
+        if self.compress_codec not in ('q8', 'topk'):
+            raise ValueError(f"unknown --compress-codec {self.compress_codec!r}")
+        if self.topk_k not in (4, 8, 16, 32):
+            raise ValueError(f"--topk-k must be 4, 8, 16 or 32, got "
+                             f"{self.topk_k!r}")
         if self.loader not in ('torch', 'fused'):
             raise ValueError(f"unknown --loader {self.loader!r}")
         if self.mode not in ('normal', 'kill', 'timeout'):
@@ -187,6 +206,29 @@ class JobConfig:
                           "(arrival-order first-k drives the kill verdict); "
                           "switching aggregation to 'gather'")
             self.aggregation = 'gather'
+        # The top-k codec exists only as a gather-mode payload of the PS
+        # engine (a sum of sparse payloads cannot ride a reduction) and only
+        # on the error-feedback path: without feedback most coordinates
+        # would never be sent. Anything else falls back to what the same
+        # flags do without it.
+        if self.compress_codec == 'topk':
+            import warnings
+            if self.engine != 'ps':
+                warnings.warn("--compress-codec topk applies to the PS "
+                              "engine's gather push only; --engine "
+                              f"{self.engine} runs without it")
+                self.compress_codec = 'q8'
+            elif not self.compress or self.aggregation != 'gather':
+                warnings.warn("--compress-codec topk needs --compress-grad "
+                              "compress and --aggregation gather (collective "
+                              "mode ignores gradient codecs); running "
+                              "without the topk codec")
+                self.compress_codec = 'q8'
+            elif not self.error_feedback:
+                warnings.warn("--compress-codec topk only converges with "
+                              "error feedback (unsent coordinates live in "
+                              "the residual); switching --error-feedback on")
+                self.error_feedback = True
         # Error feedback only has something to feed back where the push
         # loses bits: the int8 codec (gather + compress) or a bf16 wire under
         # an fp32 gradient. A lossless wire gets the same normalize-and-warn

@@ -69,6 +69,16 @@ def _try_load() -> None:
                                      ctypes.c_long, ctypes.c_int, ctypes.c_void_p]
         lib.ps_acc.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
                                ctypes.c_long, ctypes.c_int, ctypes.c_void_p]
+        # block top-k codec (topk.hip): payload, src, residual, n, k,
+        # src_dtype, stream / dst, payload, n, k, accumulate, stream; both
+        # return nonzero for a k they have no kernel for
+        lib.ps_pack_topk_ef.argtypes = [ctypes.c_void_p] * 3 + [
+            ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
+        lib.ps_pack_topk_ef.restype = ctypes.c_int
+        lib.ps_unpack_topk.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
+                                       ctypes.c_long, ctypes.c_int,
+                                       ctypes.c_int, ctypes.c_void_p]
+        lib.ps_unpack_topk.restype = ctypes.c_int
         lib.ps_conv_fwd.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_int] * 11 + [ctypes.c_void_p]
         lib.ps_conv_dgrad.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int] * 11 + [ctypes.c_void_p]
         lib.ps_conv_wgrad.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int] * 12 + [ctypes.c_void_p]

@@ -274,6 +274,120 @@ def unpack_q8(dst: torch.Tensor, payload: torch.Tensor,
         dst.copy_(vals)
 
 
+# ---- block top-k sparsifying codec (error-feedback path only) ----
+# Contract documented in ops/kernels/topk.hip and docs/KERNELS.md: of every
+# 256-element block of c = src + residual the K elements with the largest
+# keys (bits(|c|) << 8) | (255 - index) go on the wire as
+# [u8 idx x nblk*K][bf16 val x nblk*K]; the rest stays in the residual. The
+# CPU paths below are the gloo path and the bitwise reference of the kernels.
+
+TOPK_BLOCK = 256
+TOPK_KS = (4, 8, 16, 32)
+
+
+def _check_topk_k(k: int) -> None:
+    if k not in TOPK_KS:
+        raise ValueError(f"top-k codec keeps k in {TOPK_KS} per "
+                         f"{TOPK_BLOCK}-block, got {k!r}")
+
+
+def topk_layout(n: int, k: int):
+    """(vals_byte_offset, total_payload_bytes) for n values at k per block."""
+    _check_topk_k(k)
+    nblk = (n + TOPK_BLOCK - 1) // TOPK_BLOCK
+    return nblk * k, 3 * nblk * k
+
+
+def _check_topk_payload(payload: torch.Tensor, tot: int) -> None:
+    if payload.dtype != torch.uint8 or payload.numel() != tot:
+        raise ValueError(f"payload must be uint8[{tot}], got "
+                         f"{payload.dtype}[{payload.numel()}]")
+    if not payload.is_contiguous():
+        raise ValueError("payload must be contiguous")
+    if payload.data_ptr() % 2:
+        raise ValueError("payload must be 2-byte aligned (bf16 values)")
+
+
+def pack_topk_ef(payload: torch.Tensor, src: torch.Tensor,
+                 residual: torch.Tensor, k: int) -> None:
+    """Top-k encode c = src + residual (one f32 add) into `payload` and
+    leave what was not sent in `residual` (f32, same numel, in place).
+
+    Per 256-block the k largest keys (bits(|c_i|) << 8) | (255 - i) are sent
+    — larger magnitude first, ties to the lower index, +-Inf and NaN above
+    every finite value; positions past n in the tail block count as +0 —
+    in ascending index order, val = bf16(c_i) rounded to nearest even. The
+    residual becomes c - f32(val) where sent (exact for finite c) and c
+    elsewhere. The CPU path below is the bitwise reference of
+    ps_pack_topk_ef."""
+    n = src.numel()
+    off, tot = topk_layout(n, k)
+    _check_topk_payload(payload, tot)
+    if src.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError("top-k source must be f32 or bf16")
+    _check_flat(src, "src", n)
+    _check_residual(residual, src)
+    if payload.device != src.device:
+        raise ValueError("payload and src must live on the same device")
+    if src.is_cuda:
+        if require_lib().ps_pack_topk_ef(payload.data_ptr(), src.data_ptr(),
+                                         residual.data_ptr(), n, k,
+                                         dtype_tag(src.dtype),
+                                         current_stream_ptr()):
+            raise RuntimeError(f"ps_pack_topk_ef has no kernel for k={k}")
+        return
+    nblk = off // k
+    cb = torch.zeros(nblk * TOPK_BLOCK, dtype=torch.float32)
+    cb[:n] = src.to(torch.float32) + residual
+    cb = cb.view(nblk, TOPK_BLOCK)
+    # integer keys are unique, so topk's choice is fully determined (a float
+    # topk would leave the order of ties open)
+    mag = (cb.view(torch.int32) & 0x7fffffff).to(torch.int64)
+    key = (mag << 8) | (255 - torch.arange(TOPK_BLOCK, dtype=torch.int64))
+    idx = torch.topk(key, k, dim=1).indices.sort(dim=1).values
+    sent = cb.gather(1, idx)
+    vals = sent.to(torch.bfloat16)
+    payload[:off] = idx.to(torch.uint8).view(-1)
+    payload[off:] = vals.contiguous().view(-1).view(torch.uint8)
+    cb.scatter_(1, idx, sent - vals.to(torch.float32))
+    residual.copy_(cb.view(-1)[:n])
+
+
+def unpack_topk(dst: torch.Tensor, payload: torch.Tensor, k: int,
+                accumulate: bool = False) -> None:
+    """Decode a top-k `payload` into f32 `dst`: zero-fill unless
+    `accumulate`, then for every block and j = 0..k-1 in payload order
+    dst[blk*256 + idx_j] += f32(val_j) where that position is < n. Indices
+    may repeat (a killed worker's all-zero payload adds +0 to element 0 of
+    each block k times); the add order is fixed, no atomics."""
+    n = dst.numel()
+    off, tot = topk_layout(n, k)
+    _check_topk_payload(payload, tot)
+    if dst.dtype != torch.float32:
+        raise TypeError("top-k destination must be f32")
+    _check_flat(dst, "dst", n)
+    if payload.device != dst.device:
+        raise ValueError("payload and dst must live on the same device")
+    if dst.is_cuda:
+        if require_lib().ps_unpack_topk(dst.data_ptr(), payload.data_ptr(),
+                                        n, k, int(accumulate),
+                                        current_stream_ptr()):
+            raise RuntimeError(f"ps_unpack_topk has no kernel for k={k}")
+        return
+    nblk = off // k
+    idx = payload[:off].view(nblk, k).to(torch.int64)
+    vals = payload[off:].clone().view(torch.bfloat16).view(nblk, k).to(
+        torch.float32)
+    base = torch.arange(nblk, dtype=torch.int64) * TOPK_BLOCK
+    if not accumulate:
+        dst.zero_()
+    for j in range(k):
+        # one entry per block: positions within a pass are distinct
+        pos = base + idx[:, j]
+        live = pos < n
+        dst[pos[live]] += vals[:, j][live]
+
+
 def acc_into(acc: torch.Tensor, src: torch.Tensor) -> None:
     """acc += src (f32 acc; f32/bf16 src) — PS fan-in accumulate for
     uncompressed gather mode (the reference's Waitany += loop,

@@ -67,7 +67,8 @@ class ParameterServer:
         self.network = net
         self.flat = FlatSpace(net, bucket_bytes=int(cfg.bucket_mb * 2 ** 20))
         # --compress-grad encodes per mode: gather -> block-scaled int8
-        # payloads (4x, quant.hip); collective -> bf16 wire (2x) since a
+        # payloads (4x, quant.hip) or, with --compress-codec topk, block
+        # top-k payloads (topk.hip); collective -> bf16 wire (2x) since a
         # summed int8 payload can't ride an in-flight ncclReduce.
         self.transport = PSTransport(self.flat, self.wire_dtype, self.device,
                                      self.rank, self.world,
@@ -75,7 +76,9 @@ class ParameterServer:
                                      compress=cfg.compress,
                                      comm_type=cfg.comm_type,
                                      track_killed=(cfg.mode == 'timeout'
-                                                   and cfg.aggregation == 'gather'))
+                                                   and cfg.aggregation == 'gather'),
+                                     codec=cfg.compress_codec,
+                                     topk_k=cfg.topk_k)
         self.ctrl = (ControlPlane(self.rank, self.world)
                      if cfg.mode == 'kill' else None)
         if cfg.resume_step:

@@ -19,6 +19,9 @@ bucketed collectives on ONE flat buffer over `torch.distributed`
   compression                    -> gather mode sends block-scaled int8
         payloads (ops/kernels/quant.hip, 4x smaller than f32) — the GPU
         re-expression of blosc g_compress (ref compression.py:18-46).
+        --compress-codec topk sends the K largest magnitudes of every 256
+        elements instead (ops/kernels/topk.hip, 3*K bytes per block) and
+        carries the rest in the error-feedback residual.
         Both wire codecs (int8, and bf16 under an f32 gradient) are lossy
         where blosc was not; --error-feedback keeps each worker's rounding
         error in a local f32 residual and re-injects it next step.
@@ -77,7 +80,7 @@ class PSTransport:
                the PS; the reduce source on workers)
     Gather mode adds:
       payload   (worker) / stages[w] (PS) : per-bucket P2P gradient payloads
-               (q8-compressed bytes, or wire-dtype values)
+               (q8- or topk-compressed bytes, or wire-dtype values)
       acc_g (PS) : f32 arrival-order accumulator consumed by the optimizer
     """
 
@@ -86,9 +89,12 @@ class PSTransport:
                  group: Optional[dist.ProcessGroup] = None,
                  mode: str = 'collective', compress: bool = False,
                  comm_type: str = 'Bcast', track_killed: bool = False,
-                 error_feedback: bool = False):
+                 error_feedback: bool = False, codec: str = 'q8',
+                 topk_k: int = 16):
         if mode not in ('collective', 'gather'):
             raise ValueError(f"unknown aggregation mode {mode!r}")
+        if codec not in ('q8', 'topk'):
+            raise ValueError(f"unknown gradient codec {codec!r}")
         self.comm_type = comm_type
         self.flat = flat
         self.rank = rank
@@ -98,6 +104,17 @@ class PSTransport:
         self.wire_dtype = wire_dtype
         self.mode = mode
         self.compress = bool(compress) and mode == 'gather'
+        # gather-mode payload codec: 'q8' (block-scaled int8) or 'topk'
+        # (topk_k of every 256 elements, the rest carried in the residual).
+        # top-k is defined on the feedback path only, so it implies the
+        # residual below.
+        self.codec = codec if self.compress else None
+        self.topk_k = int(topk_k)
+        if self.codec == 'topk':
+            if self.topk_k not in ops_f.TOPK_KS:
+                raise ValueError(f"topk_k must be one of {ops_f.TOPK_KS}, "
+                                 f"got {topk_k!r}")
+            error_feedback = True
         # liveness bound for the PS fan-in (a crashed worker otherwise hangs
         # the drain forever — the reference shares this property, but an
         # 8-GPU production run deserves a loud error over a silent hang)
@@ -157,11 +174,14 @@ class PSTransport:
 
         if mode == 'gather':
             if self.compress:
-                # per-bucket q8 payload framing inside ONE byte buffer
+                # per-bucket codec payload framing inside ONE byte buffer
                 self._pl_off: List[tuple] = []
                 cur = 0
                 for b in flat.buckets:
-                    _, tot = ops_f.q8_layout(b.numel)
+                    if self.codec == 'topk':
+                        _, tot = ops_f.topk_layout(b.numel, self.topk_k)
+                    else:
+                        _, tot = ops_f.q8_layout(b.numel)
                     self._pl_off.append((cur, tot))
                     cur += tot
                 self.payload_bytes = cur
@@ -195,7 +215,10 @@ class PSTransport:
         broadcasts a fingerprint of FlatSpace.layout_signature(); a
         divergent rank raises instead of silently mis-framing payloads."""
         import zlib
-        sig = zlib.crc32(repr(self.flat.layout_signature()).encode())
+        # the payload framing follows the codec and its K as well
+        codec = (self.codec, self.topk_k if self.codec == 'topk' else None)
+        sig = zlib.crc32(
+            repr((self.flat.layout_signature(), codec)).encode())
         dev = (self.device if dist.get_backend(self.group) == 'nccl'
                else torch.device('cpu'))
         t = torch.tensor([sig], dtype=torch.int64, device=dev)
@@ -323,7 +346,11 @@ class PSTransport:
                 payload = self._zero_payload[:self._pl_off[b.index][1]]
             else:
                 payload = self._worker_payload_slice(b)
-                if self.ef_active:
+                if self.codec == 'topk':
+                    ops_f.pack_topk_ef(payload, self.flat.grad_slice(b),
+                                       self.residual[b.start:b.end],
+                                       self.topk_k)
+                elif self.ef_active:
                     ops_f.pack_q8_ef(payload, self.flat.grad_slice(b),
                                      self.residual[b.start:b.end])
                 else:
@@ -414,7 +441,11 @@ class PSTransport:
                 killed_of[w] = self._recv_killed_flag(w)
             if counts[bi] < k and not killed_of.get(w, False):
                 b = buckets[bi]
-                if self.compress:
+                if self.codec == 'topk':
+                    ops_f.unpack_topk(self.acc_g[b.start:b.end],
+                                      self._stage_slice(w, b), self.topk_k,
+                                      accumulate=True)
+                elif self.compress:
                     ops_f.unpack_q8(self.acc_g[b.start:b.end],
                                     self._stage_slice(w, b), accumulate=True)
                 else:

@@ -83,7 +83,9 @@ class DistributedWorker:
                                      comm_type=cfg.comm_type,
                                      track_killed=(cfg.mode == 'timeout'
                                                    and cfg.aggregation == 'gather'),
-                                     error_feedback=cfg.error_feedback)
+                                     error_feedback=cfg.error_feedback,
+                                     codec=cfg.compress_codec,
+                                     topk_k=cfg.topk_k)
         # straggler handling (ref resnet_split.py:503-728): 'kill' polls the
         # PS's gloo signal from backward hooks; 'timeout' aborts locally past
         # --kill-threshold seconds. Both raise StepKilled mid-backward and

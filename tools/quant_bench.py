@@ -1,5 +1,6 @@
 #!/usr/bin/env python
-"""Time of the gradient wire packs with and without error feedback.
+"""Time of the gradient wire codecs: the packs with and without error
+feedback, the block top-k codec, and the PS-side decodes.
 
   python tools/quant_bench.py [--n 11200000] [--sets 4] [--steps 2000]
                               [--warmup 20] [--rounds 5] [--eager]
@@ -7,18 +8,27 @@
 
 Times pack_q8 against pack_q8_ef (f32 and bf16 sources) and pack_wire
 f32->bf16 against pack_wire_ef on `n` elements (default 11.2 M, ResNet-18's
-flat gradient). HIP events around one replay of a graph of `steps`
-back-to-back launches (mean per launch, kernel boundaries included),
-`rounds` alternating rounds of every variant, median reported.
+flat gradient), and next to them the block top-k codec: pack_topk_ef (f32
+and bf16 sources) for every K, its worst case (`_ties`: all-equal blocks,
+on which the threshold search cannot stop early), and the accumulating
+decodes unpack_topk and
+unpack_q8 the PS runs per arrival. HIP events around one replay of a graph
+of `steps` back-to-back launches (mean per launch, kernel boundaries
+included), `rounds` alternating rounds of every variant, median reported.
 GB/s counts the bytes each kernel actually moves: source read, payload
-write, and for the EF kernels one f32 residual read and one write per
-element. Launches rotate over `sets` independent buffer sets so that with
-the default 4 the working set (~400 MB) does not fit the 256 MiB Infinity
+write, for the EF kernels one f32 residual read and one write per element,
+and for the decodes the payload read plus one f32 accumulator read and
+write. Launches rotate over `sets` independent buffer sets (the EF packs
+carry their residual from launch to launch, as training does) so that with
+the default 4 the working set (~1.1 GB) does not fit the 256 MiB Infinity
 Cache; --sets 1 gives the cache-resident figure instead.
 
 --baseline-lib names another build of the kernel library (the parent
 commit's, say); its plain packs are timed in the same rounds on the same
-buffers, and the ratio to this build's is reported. Prints one JSON line.
+buffers, and the ratio to this build's is reported. Prints one JSON line;
+`wire_bytes_per_elem` is the payload size of each codec per gradient
+element, and `time_ratio` holds every top-k row against its q8 counterpart
+(pack_q8_ef of the same source, unpack_q8) from the same run.
 """
 from __future__ import annotations
 
@@ -112,7 +122,13 @@ def main(argv=None) -> None:
             'f32': x, 'bf16': x.to(torch.bfloat16),
             'res': torch.randn(n, device='cuda', generator=g) * 1e-4,
             'payload': torch.zeros(tot, dtype=torch.uint8, device='cuda'),
-            'wire': torch.zeros(n, dtype=torch.bfloat16, device='cuda')})
+            'wire': torch.zeros(n, dtype=torch.bfloat16, device='cuda'),
+            'acc': torch.zeros(n, device='cuda'),
+            'zero': torch.zeros(n, device='cuda'),
+            'zero_res': torch.zeros(n, device='cuda'),
+            # sliced per K; any bytes decode (u8 index, bf16 value)
+            'tk_payload': torch.zeros(F.topk_layout(n, max(F.TOPK_KS))[1],
+                                      dtype=torch.uint8, device='cuda')})
 
     q8_bytes = n + 4 * nblk
     variants = {}   # name -> (calls, bytes moved per launch)
@@ -129,6 +145,29 @@ def main(argv=None) -> None:
                     s['payload'].data_ptr(), s[k].data_ptr(), n,
                     dtype_tag(s[k].dtype), current_stream_ptr())
                  for s in sets], sz * n + q8_bytes)
+        for k in F.TOPK_KS:
+            tk = F.topk_layout(n, k)[1]
+            variants[f'pack_topk_ef_{src}_k{k}'] = (
+                [lambda s=s, key=src, k=k, tk=tk: F.pack_topk_ef(
+                    s['tk_payload'][:tk], s[key], s['res'], k)
+                 for s in sets], sz * n + tk + 8 * n)
+    # the threshold search stops early on distinct magnitudes; all-equal
+    # blocks (here: zeros, which stay zeros) take every round — the worst case
+    tk = F.topk_layout(n, 16)[1]
+    variants['pack_topk_ef_f32_k16_ties'] = (
+        [lambda s=s, tk=tk: F.pack_topk_ef(s['tk_payload'][:tk], s['zero'],
+                                           s['zero_res'], 16)
+         for s in sets], 4 * n + tk + 8 * n)
+    # the PS-side decodes, accumulating as the drain does
+    variants['unpack_q8'] = (
+        [lambda s=s: F.unpack_q8(s['acc'], s['payload'], accumulate=True)
+         for s in sets], q8_bytes + 8 * n)
+    for k in F.TOPK_KS:
+        tk = F.topk_layout(n, k)[1]
+        variants[f'unpack_topk_k{k}'] = (
+            [lambda s=s, k=k, tk=tk: F.unpack_topk(
+                s['acc'], s['tk_payload'][:tk], k, accumulate=True)
+             for s in sets], tk + 8 * n)
     variants['pack_wire_bf16'] = (
         [lambda s=s: F.pack_wire(s['wire'], s['f32']) for s in sets], 6 * n)
     variants['pack_wire_ef_bf16'] = (
@@ -163,7 +202,19 @@ def main(argv=None) -> None:
             ratios[f'{plain}/baseline'] = round(
                 out[plain]['us_median']
                 / out[f'baseline_{plain}']['us_median'], 3)
+    for k in F.TOPK_KS:
+        for src in ('f32', 'bf16'):
+            ratios[f'pack_topk_ef_{src}_k{k}/pack_q8_ef_{src}'] = round(
+                out[f'pack_topk_ef_{src}_k{k}']['us_median']
+                / out[f'pack_q8_ef_{src}']['us_median'], 3)
+        ratios[f'unpack_topk_k{k}/unpack_q8'] = round(
+            out[f'unpack_topk_k{k}']['us_median']
+            / out['unpack_q8']['us_median'], 3)
     out['time_ratio'] = ratios
+    wire = {'f32': 4.0, 'bf16': 2.0, 'q8': round(q8_bytes / n, 4)}
+    for k in F.TOPK_KS:
+        wire[f'topk_k{k}'] = round(F.topk_layout(n, k)[1] / n, 4)
+    out['wire_bytes_per_elem'] = wire
     print(json.dumps(out))
 
 
