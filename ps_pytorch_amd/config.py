@@ -106,6 +106,18 @@ def add_fit_args(parser: argparse.ArgumentParser) -> argparse.ArgumentParser:
                         help='4 | 8 | 16 | 32 : elements kept per 256-block '
                              'by --compress-codec topk (3*K bytes per block '
                              'on the wire)')
+    parser.add_argument('--fan-in', type=str, default='arrival',
+                        help='arrival | fused : PS-side gradient fan-in of '
+                             '--aggregation gather. arrival = every payload '
+                             'is accumulated as it arrives (the sum is taken '
+                             'in arrival order), then one optimizer pass; '
+                             'fused = once a bucket\'s first --num-aggregate '
+                             'workers are known, one kernel decodes their '
+                             'payloads, sums them in ascending worker rank, '
+                             'applies the update to that slice and re-packs '
+                             'its broadcast payload: the result depends on '
+                             'which workers counted, not on their arrival '
+                             'order (at most 16 workers)')
     parser.add_argument('--resume-step', type=int, default=0,
                         help='warm-start: load train-dir/model_step_<K> '
                              'into the global model before training '
@@ -179,8 +191,11 @@ class JobConfig:
     train_metrics: bool = False
     compress_codec: str = 'q8'
     topk_k: int = 16
+    fan_in: str = 'arrival'
 
     def __post_init__(self) -> None:
+        if self.fan_in not in ('arrival', 'fused'):
+            raise ValueError(f"unknown --fan-in {self.fan_in!r}")
         if self.compress_codec not in ('q8', 'topk'):
             raise ValueError(f"unknown --compress-codec {self.compress_codec!r}")
         if self.topk_k not in (4, 8, 16, 32):
@@ -206,6 +221,22 @@ class JobConfig:
                           "(arrival-order first-k drives the kill verdict); "
                           "switching aggregation to 'gather'")
             self.aggregation = 'gather'
+        # The fused fan-in replaces the PS's per-arrival accumulate of the
+        # gather drain; a collective reduce sums in flight and the allreduce
+        # engine has no PS, so there is nothing for it to fuse there.
+        if self.fan_in == 'fused':
+            import warnings
+            if self.engine != 'ps':
+                warnings.warn("--fan-in fused applies to the PS engine's "
+                              f"gather fan-in only; --engine {self.engine} "
+                              "runs without it")
+                self.fan_in = 'arrival'
+            elif self.aggregation != 'gather':
+                warnings.warn("--fan-in fused needs --aggregation gather "
+                              "(a collective reduce has no per-worker "
+                              "payloads to fuse); running the arrival "
+                              "fan-in")
+                self.fan_in = 'arrival'
         # The top-k codec exists only as a gather-mode payload of the PS
         # engine (a sum of sparse payloads cannot ride a reduction) and only
         # on the error-feedback path: without feedback most coordinates

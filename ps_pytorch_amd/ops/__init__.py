@@ -79,6 +79,19 @@ def _try_load() -> None:
                                        ctypes.c_long, ctypes.c_int,
                                        ctypes.c_int, ctypes.c_void_p]
         lib.ps_unpack_topk.restype = ctypes.c_int
+        # rank-ordered fan-in (fanin.hip): dst, srcs (host array of device
+        # pointers), nsrc, codec, k, n, stream / w, m, wire, wire_dtype,
+        # srcs, nsrc, codec, k, n, lr, mu, wd, scale, nesterov, stream;
+        # both return nonzero and launch nothing for arguments they reject
+        lib.ps_fanin_reduce.argtypes = [
+            ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int,
+            ctypes.c_int, ctypes.c_int, ctypes.c_long, ctypes.c_void_p]
+        lib.ps_fanin_reduce.restype = ctypes.c_int
+        lib.ps_fanin_sgd.argtypes = [ctypes.c_void_p] * 3 + [
+            ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int,
+            ctypes.c_int, ctypes.c_int, ctypes.c_long] + [
+            ctypes.c_float] * 4 + [ctypes.c_int, ctypes.c_void_p]
+        lib.ps_fanin_sgd.restype = ctypes.c_int
         lib.ps_conv_fwd.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_int] * 11 + [ctypes.c_void_p]
         lib.ps_conv_dgrad.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int] * 11 + [ctypes.c_void_p]
         lib.ps_conv_wgrad.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int] * 12 + [ctypes.c_void_p]

@@ -404,6 +404,161 @@ def acc_into(acc: torch.Tensor, src: torch.Tensor) -> None:
     acc.add_(src.to(torch.float32))
 
 
+# ---- rank-ordered fan-in (ops/kernels/fanin.hip) ----
+# One launch decodes up to 16 staged payloads of one bucket and sums them in
+# the order given: s = +0; s = s + dec_j, one f32 add per source. raw: dec is
+# the (widened) value; q8: dec = f32(q) * scale, a rounded multiply and then
+# the add (no fma); topk: a source's entries are added in payload order. The
+# CPU paths below are the gloo path and the bitwise reference of the kernels.
+
+FANIN_MAX_SRCS = 16
+FANIN_CODECS = ('raw', 'q8', 'topk')
+_FANIN_F32, _FANIN_BF16, _FANIN_Q8, _FANIN_TOPK = 0, 1, 2, 3
+
+
+def _fanin_check(n: int, device, srcs, codec: str, k) -> int:
+    """Validate the sources of one fan-in over n elements; returns the codec
+    tag of the native entry points."""
+    if codec not in FANIN_CODECS:
+        raise ValueError(f"unknown fan-in codec {codec!r}, one of "
+                         f"{FANIN_CODECS}")
+    if len(srcs) > FANIN_MAX_SRCS:
+        raise ValueError(f"fan-in takes at most {FANIN_MAX_SRCS} sources, "
+                         f"got {len(srcs)}")
+    if codec == 'topk':
+        _, tot = topk_layout(n, k)          # raises for a bad k
+        for s in srcs:
+            _check_topk_payload(s, tot)
+        tag = _FANIN_TOPK
+    elif codec == 'q8':
+        _, tot = q8_layout(n)
+        for s in srcs:
+            if s.dtype != torch.uint8 or s.numel() != tot:
+                raise ValueError(f"payload must be uint8[{tot}], got "
+                                 f"{s.dtype}[{s.numel()}]")
+        tag = _FANIN_Q8
+    else:
+        dt = srcs[0].dtype if srcs else torch.float32
+        if dt not in (torch.float32, torch.bfloat16):
+            raise TypeError("raw fan-in sources must be f32 or bf16")
+        for s in srcs:
+            if s.dtype != dt:
+                raise TypeError("raw fan-in sources must share one dtype")
+            _check_flat(s, "src", n)
+        tag = _FANIN_BF16 if dt == torch.bfloat16 else _FANIN_F32
+    for s in srcs:
+        if not s.is_contiguous():
+            raise ValueError("fan-in sources must be contiguous")
+        if s.device != device:
+            raise ValueError("fan-in sources and outputs must live on the "
+                             "same device")
+    return tag
+
+
+def _fanin_device_args(n: int, srcs, tag: int, outs):
+    """Alignment checks of the vector kernels and the host pointer array."""
+    import ctypes
+    if n % 4:
+        raise ValueError("flat buffers must be padded to a multiple of 4")
+    # payload byte buffers: q8 4 B (char4 quants, f32 scales), top-k 2 B
+    # (bf16 values); raw sources are read as whole quads
+    align = {_FANIN_F32: 16, _FANIN_BF16: 8, _FANIN_Q8: 4, _FANIN_TOPK: 2}[tag]
+    for s in srcs:
+        if s.data_ptr() % align:
+            raise ValueError(f"fan-in source must be {align}-byte aligned")
+    for name, t in outs:
+        if t is not None and t.data_ptr() % (4 * t.element_size()):
+            raise ValueError(f"{name} must be aligned to 4 elements")
+    return (ctypes.c_void_p * FANIN_MAX_SRCS)(*[s.data_ptr() for s in srcs])
+
+
+def _fanin_raise(entry: str, rc: int, nsrc: int, codec: str, k, n: int):
+    raise RuntimeError(f"{entry} launched nothing (code {rc}): nsrc={nsrc}, "
+                       f"codec={codec!r}, k={k!r}, n={n}")
+
+
+def fanin_reduce(dst: torch.Tensor, srcs, codec: str, k=None) -> None:
+    """dst (f32) = the sum of the decoded `srcs` taken strictly in list
+    order, starting from +0 (an empty list zero-fills). codec: 'raw' (f32 or
+    bf16 tensors of dst's numel), 'q8' (pack_q8 payloads) or 'topk'
+    (pack_topk_ef payloads at `k` per block)."""
+    n = dst.numel()
+    srcs = list(srcs)
+    if dst.dtype != torch.float32:
+        raise TypeError("fan-in destination must be f32")
+    _check_flat(dst, "dst", n)
+    tag = _fanin_check(n, dst.device, srcs, codec, k)
+    if dst.is_cuda:
+        ptrs = _fanin_device_args(n, srcs, tag, [("dst", dst)])
+        rc = require_lib().ps_fanin_reduce(
+            dst.data_ptr(), ptrs, len(srcs), tag,
+            int(k) if codec == 'topk' else 0, n, current_stream_ptr())
+        if rc:
+            _fanin_raise('ps_fanin_reduce', rc, len(srcs), codec, k, n)
+        return
+    s = torch.zeros(n, dtype=torch.float32)
+    if codec == 'topk':
+        off, _ = topk_layout(n, k)
+        nblk = off // k
+        base = torch.arange(nblk, dtype=torch.int64) * TOPK_BLOCK
+    elif codec == 'q8':
+        qb, _ = q8_layout(n)
+        nblk = (n + Q8_BLOCK - 1) // Q8_BLOCK
+    for p in srcs:
+        if codec == 'topk':
+            idx = p[:off].view(nblk, k).to(torch.int64)
+            vals = p[off:].clone().view(torch.bfloat16).view(nblk, k).to(
+                torch.float32)
+            for j in range(k):
+                # one entry per block: positions within a pass are distinct
+                pos = base + idx[:, j]
+                live = pos < n
+                s[pos[live]] += vals[:, j][live]
+        elif codec == 'q8':
+            q = p[:n].view(torch.int8).to(torch.float32)
+            scales = p[qb:qb + 4 * nblk].clone().view(torch.float32)
+            dec = q * scales.repeat_interleave(Q8_BLOCK)[:n]   # rounded once
+            s = s + dec                                        # then the add
+        else:
+            s = s + p.to(torch.float32)
+    dst.copy_(s)
+
+
+def fanin_sgd(w: torch.Tensor, m: torch.Tensor, srcs, codec: str, k,
+              lr: float, momentum: float = 0.0, weight_decay: float = 0.0,
+              grad_scale: float = 1.0, nesterov: bool = False,
+              wire_out: Optional[torch.Tensor] = None) -> None:
+    """fanin_reduce followed by fused_sgd_step on the sum; on the GPU one
+    launch in which the sum never reaches memory. Bitwise equal to the
+    two-step form."""
+    n = w.numel()
+    srcs = list(srcs)
+    if w.dtype != torch.float32 or m.dtype != torch.float32:
+        raise TypeError("master weights and momentum must be f32")
+    _check_flat(w, "w", n)
+    _check_flat(m, "momentum_buf", n)
+    if wire_out is not None:
+        _check_flat(wire_out, "wire_out", n)
+    tag = _fanin_check(n, w.device, srcs, codec, k)
+    if w.is_cuda:
+        ptrs = _fanin_device_args(n, srcs, tag, [("w", w), ("m", m),
+                                                 ("wire_out", wire_out)])
+        rc = require_lib().ps_fanin_sgd(
+            w.data_ptr(), m.data_ptr(),
+            0 if wire_out is None else wire_out.data_ptr(),
+            dtype_tag(wire_out.dtype) if wire_out is not None else 0,
+            ptrs, len(srcs), tag, int(k) if codec == 'topk' else 0, n,
+            float(lr), float(momentum), float(weight_decay),
+            float(grad_scale), int(nesterov), current_stream_ptr())
+        if rc:
+            _fanin_raise('ps_fanin_sgd', rc, len(srcs), codec, k, n)
+        return
+    g = torch.empty(n, dtype=torch.float32)
+    fanin_reduce(g, srcs, codec, k)
+    fused_sgd_step(w, g, m, lr, momentum, weight_decay, grad_scale, nesterov,
+                   wire_out)
+
+
 # ---- counter-based dropout (CPU oracle for ops/kernels/dropout.hip) ----
 # Philox4x32-10; element e takes word (e & 3) of the block whose counter is
 # (lo32(e>>2), hi32(e>>2), step, (stream << 16) | salt) under key

@@ -13,7 +13,9 @@
 // Memory-bound: reads w, m, g; writes w, m, wire — fusing avoids 3 extra
 // round trips over the ~45 MB (ResNet-18) flat buffer at ~6.3 TB/s HBM.
 // Vectorized 4 elements/lane (float4 / ushort4 paths), grid-stride.
+// The per-element update lives in sgd_update.h, shared with fanin.hip.
 #include "common.h"
+#include "sgd_update.h"
 
 template <typename GV, typename WIREV, bool NESTEROV, bool HAS_WIRE, bool HAS_WD>
 __global__ __launch_bounds__(256) void fused_sgd_kernel(
@@ -36,12 +38,9 @@ __global__ __launch_bounds__(256) void fused_sgd_kernel(
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            float gk = gv[k] * scale;
-            if constexpr (HAS_WD) gk = fmaf(wd, wv[k], gk);
-            float mk = fmaf(mu, mv[k], gk);
-            mv[k] = mk;
-            float upd = NESTEROV ? fmaf(mu, mk, gk) : mk;
-            wv[k] = fmaf(-lr, upd, wv[k]);
+            float wk = wv[k], mk = mv[k];
+            sgd_update_elem(wk, mk, gv[k], scale, lr, mu, wd, HAS_WD, NESTEROV);
+            wv[k] = wk; mv[k] = mk;
         }
         ((float4_t*)w)[i] = wv;
         ((float4_t*)m)[i] = mv;

@@ -13,7 +13,7 @@ from typing import Optional
 
 import torch
 
-from ..ops.functional import fused_sgd_step
+from ..ops.functional import fanin_sgd, fused_sgd_step
 
 
 class FlatSGD:
@@ -43,6 +43,19 @@ class FlatSGD:
             return
         fused_sgd_step(self.w, grad_sum, self.m, self.lr, self.momentum,
                        self.weight_decay, grad_scale, self.nesterov, wire_out)
+
+    @torch.no_grad()
+    def step_fanin(self, srcs, codec: str, k=None, grad_scale: float = 1.0,
+                   wire_out: Optional[torch.Tensor] = None,
+                   region=None) -> None:
+        """step() on the rank-ordered sum of the staged payloads `srcs`
+        (ops.functional.fanin_sgd): the gather-mode PS's fused fan-in, one
+        launch per bucket, the sum never materialised. region=(start, end)
+        is the flat slice the payloads cover (default: everything)."""
+        st, en = region if region is not None else (0, self.w.numel())
+        fanin_sgd(self.w[st:en], self.m[st:en], srcs, codec, k, self.lr,
+                  self.momentum, self.weight_decay, grad_scale, self.nesterov,
+                  wire_out[st:en] if wire_out is not None else None)
 
     def state_dict(self) -> dict:
         return {'momentum_buffer': self.m, 'lr': self.lr,

@@ -26,6 +26,7 @@ import torch.distributed as dist
 
 from ..config import JobConfig, input_shape_of, num_classes_of
 from ..models import build_model
+from ..ops import functional as ops_f
 from ..optim import FlatAdam, FlatSGD
 from ..parallel.flat import FlatSpace, prep_model
 from ..parallel.transport import ControlPlane, PSTransport
@@ -52,6 +53,16 @@ class ParameterServer:
         self.wire_dtype = (torch.bfloat16
                            if (cfg.compress or cfg.wire_dtype == 'bf16') and device.type == 'cuda'
                            else torch.float32)
+        # --fan-in fused (gather mode): set-ordered fused fan-in + update per
+        # bucket; its kernel takes at most 16 payload pointers per launch
+        self.fan_in = getattr(cfg, 'fan_in', 'arrival')
+        if (self.fan_in == 'fused'
+                and world - 1 > ops_f.FANIN_MAX_SRCS):
+            import warnings
+            warnings.warn(f"--fan-in fused sums at most "
+                          f"{ops_f.FANIN_MAX_SRCS} workers per launch; "
+                          f"{world - 1} workers run the arrival fan-in")
+            self.fan_in = 'arrival'
         self.cur_step = 0
         self.network = None
         self.flat: Optional[FlatSpace] = None
@@ -114,6 +125,8 @@ class ParameterServer:
         if t.bcast_bucketed:
             return self._step_pipelined()
         t.broadcast_weights()
+        if t.mode == 'gather' and self.fan_in == 'fused':
+            return self._step_fused_fanin()
         if t.mode == 'gather':
             t.post_gather_recvs()
             on_quota = self.ctrl.signal if self.ctrl is not None else None
@@ -133,6 +146,27 @@ class ParameterServer:
         # fused: average-scale + momentum + update + re-pack next payload
         self.optimizer.step(grad, grad_scale=self.grad_scale,
                             wire_out=t.wire_w)
+        self.cur_step += 1
+
+    def _step_fused_fanin(self) -> None:
+        """Gather mode with --fan-in fused: every bucket is applied the
+        moment its set of counted workers is final, inside the drain — one
+        launch that decodes the selected payloads, sums them in ascending
+        worker rank, averages over the workers actually counted, updates
+        that slice of the master weights and re-packs its broadcast payload
+        (FlatAdam: a rank-ordered sum into acc_g plus a slice step). No
+        accumulator zero pass, no whole-buffer optimizer call."""
+        t = self.transport
+        t.post_gather_recvs()
+        on_quota = self.ctrl.signal if self.ctrl is not None else None
+        applied = [0]
+
+        def apply(b, workers):
+            t.fused_apply(b, workers, self.optimizer, wire_out=t.wire_w,
+                          advance=(applied[0] == 0))
+            applied[0] += 1
+
+        t.drain_fused(self.cfg.num_aggregate, apply, on_quota=on_quota)
         self.cur_step += 1
 
     def _step_pipelined(self) -> None:

@@ -16,6 +16,10 @@ bucketed collectives on ONE flat buffer over `torch.distributed`
         Waitany-drain semantics (sync_replicas_master_nn.py:157-186) and
         enables --num-aggregate first-k selection and the compressed
         payload (summed payloads can't ride an in-flight reduction).
+        --fan-in fused keeps the selection by arrival but sums a bucket's
+        selected payloads in ascending worker rank, in ONE launch that also
+        applies the update and re-packs the broadcast slice
+        (drain_fused / fused_apply, ops/kernels/fanin.hip).
   compression                    -> gather mode sends block-scaled int8
         payloads (ops/kernels/quant.hip, 4x smaller than f32) — the GPU
         re-expression of blosc g_compress (ref compression.py:18-46).
@@ -459,6 +463,75 @@ class PSTransport:
         if on_quota is not None and not quota_fired:
             on_quota([])
         return counts
+
+    # -- gather mode, PS side: fused (set-ordered) fan-in --
+
+    def drain_fused(self, num_aggregate: int, on_final,
+                    on_quota=None) -> List[int]:
+        """PS: the --fan-in fused drain. Which workers count for a bucket is
+        decided exactly as in drain_arrivals — the first `num_aggregate`
+        arrivals not flagged killed — but nothing is accumulated on arrival:
+        a bucket is final at the earlier of its k-th counted arrival and its
+        last arrival, and `on_final(bucket, workers)` is called then with the
+        selected worker ranks in ascending order (possibly none). What is
+        computed from a bucket therefore depends on the selected set only,
+        not on the order its members arrived in. `on_quota`, the killed-flag
+        channel, the drain timeout and the returned counts are those of
+        drain_arrivals."""
+        assert self.rank == PS_RANK and self.mode == 'gather'
+        buckets = self.flat.buckets
+        k = max(1, min(num_aggregate, self.world - 1))
+        counts = [0] * len(buckets)
+        seen = [0] * len(buckets)
+        selected: List[List[int]] = [[] for _ in buckets]
+        final = [False] * len(buckets)
+        left = {w: len(buckets) for w in range(1, self.world)}
+        killed_of: dict = {}
+        quota_fired = False
+        for bi, w in self._arrivals():
+            left[w] -= 1
+            if self.track_killed and w not in killed_of:
+                killed_of[w] = self._recv_killed_flag(w)
+            seen[bi] += 1
+            if counts[bi] < k and not killed_of.get(w, False):
+                selected[bi].append(w)
+                counts[bi] += 1
+            if not final[bi] and (counts[bi] >= k
+                                  or seen[bi] == self.world - 1):
+                final[bi] = True
+                on_final(buckets[bi], sorted(selected[bi]))
+            if (on_quota is not None and not quota_fired
+                    and all(c >= k for c in counts)):
+                quota_fired = True
+                on_quota(sorted(w for w, n in left.items() if n > 0))
+        if on_quota is not None and not quota_fired:
+            on_quota([])
+        return counts
+
+    def fused_apply(self, b: Bucket, workers, optimizer,
+                    wire_out: Optional[torch.Tensor] = None,
+                    advance: bool = True) -> None:
+        """PS: apply bucket `b` from the staged payloads of `workers` (1-based
+        ranks, summed in the order given — drain_fused hands them over
+        ascending). The average is one scale 1/len(workers); with no worker
+        the gradient is +0 at scale 1 (momentum still decays). An optimizer
+        with step_fanin (FlatSGD) gets decode, sum, update and wire re-pack
+        in one launch; any other (FlatAdam) gets the rank-ordered sum in
+        acc_g[b] and a slice step, `advance` marking the first bucket of the
+        logical step. Needs no process group."""
+        assert self.rank == PS_RANK and self.mode == 'gather'
+        srcs = [self._stage_slice(w, b) for w in workers]
+        codec = self.codec or 'raw'
+        k = self.topk_k if codec == 'topk' else None
+        scale = 1.0 / len(srcs) if srcs else 1.0
+        region = (b.start, b.end)
+        if hasattr(optimizer, 'step_fanin'):
+            optimizer.step_fanin(srcs, codec, k, grad_scale=scale,
+                                 wire_out=wire_out, region=region)
+        else:
+            ops_f.fanin_reduce(self.acc_g[b.start:b.end], srcs, codec, k)
+            optimizer.step(self.acc_g, grad_scale=scale, wire_out=wire_out,
+                           region=region, advance=advance)
 
     # -- killed-flag side channel (timeout mode, gather) --
 
