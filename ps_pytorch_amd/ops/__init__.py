@@ -95,6 +95,12 @@ def _try_load() -> None:
         lib.ps_conv_fwd.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_int] * 11 + [ctypes.c_void_p]
         lib.ps_conv_dgrad.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int] * 11 + [ctypes.c_void_p]
         lib.ps_conv_wgrad.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int] * 12 + [ctypes.c_void_p]
+        # test hook: dout, in, partial, Nb, H, W, C, K, P, Q, split,
+        # variant (0 register kernel, 1 LDS-ring kernel), stream; one
+        # row-halo wgrad kernel alone, no reduce; nonzero = shape not taken
+        lib.ps_conv_wgrad_row_variant.argtypes = [ctypes.c_void_p] * 3 + [
+            ctypes.c_int] * 9 + [ctypes.c_void_p]
+        lib.ps_conv_wgrad_row_variant.restype = ctypes.c_int
         lib.ps_conv_bias_grad.argtypes = [ctypes.c_void_p] * 3 + [
             ctypes.c_long, ctypes.c_int, ctypes.c_void_p]
         lib.ps_wt_transpose.argtypes = [ctypes.c_void_p, ctypes.c_void_p,

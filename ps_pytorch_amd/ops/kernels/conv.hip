@@ -41,6 +41,12 @@
 //     LDS positions — 3x the MACs per staged byte, R instead of R*S L2
 //     re-reads. Pixel->(n,p,q) decode is shifts when the dims are powers
 //     of two (every CIFAR shape), runtime div otherwise.
+//     A row-halo step is short (12 MFMAs per wave) and the grid gives ~2
+//     blocks/CU, so the loop is LATENCY-bound, not issue-bound: aligned
+//     shapes take conv_wgrad_row_ring_kernel, which keeps 3 steps of
+//     LDS-DMA in flight through a 4-stage LDS ring (counted vmcnt, raw
+//     barrier, never vmcnt(0) in the loop) and is bit-identical to the
+//     register-staged kernel that ragged shapes keep (PS_WG_RING=0: A/B).
 //   * wgrad grids are XCD-swizzled: all blocks covering the SAME pixel
 //     chunk land on the SAME XCD (block b runs on XCD b%8) so re-reads of
 //     dout/in come from that XCD's L2, not HBM.
@@ -1334,20 +1340,34 @@ __global__ __launch_bounds__(256) void conv_wgrad_row_kernel(
     write_lds(0);
     if (nsteps > 1) load_step();
     __syncthreads();
-    for (int it = 0; it < nsteps; it += 2) {
-        if (it + 1 < nsteps) {
-            write_lds(1);
-            if (it + 2 < nsteps) load_step();
-        }
+    // full pairs with at least two more steps behind them, then the last
+    // 1..3 steps peeled: a break in the middle of the pair loop made hipcc
+    // ping-pong the 48 accumulators through a second AGPR set every pair
+    int it = 0;
+    for (; it + 3 < nsteps; it += 2) {
+        write_lds(1);
+        load_step();
         mfma_step(0);
         __syncthreads();
-        if (it + 1 >= nsteps) break;
-        if (it + 2 < nsteps) {
-            write_lds(0);
-            if (it + 3 < nsteps) load_step();
-        }
+        write_lds(0);
+        load_step();
         mfma_step(1);
         __syncthreads();
+    }
+    const int rem = nsteps - it;
+    if (rem >= 2) {
+        write_lds(1);
+        if (rem >= 3) load_step();
+    }
+    if (rem >= 1) mfma_step(0);
+    if (rem >= 2) {
+        __syncthreads();
+        if (rem >= 3) write_lds(0);
+        mfma_step(1);
+    }
+    if (rem >= 3) {
+        __syncthreads();
+        mfma_step(0);
     }
 
     const int RSC = 9 * C;
@@ -1368,21 +1388,75 @@ __global__ __launch_bounds__(256) void conv_wgrad_row_kernel(
 }
 
 
-// GLDS variant of the row-halo wgrad: both operands stage through
-// global_load_lds into LINEAR [row][128 B] images — no staging registers,
-// no guarded ds_write pass (the register/write form was issue-bound:
-// SQ_ACTIVE_INST_ANY 48%). The tr16 fragment reads move to
-// octet-swizzled positions; sigma(row, oct) = oct ^ rho(row) with
+// Ring variant of the row-halo wgrad (aligned shapes): both operands stage
+// through global_load_lds (LDS-DMA) into LINEAR [row][128 B] images — no
+// staging registers, no guarded ds_write pass — and the images live in an
+// NST-stage LDS ring with NST-1 steps of DMA in flight. A step is only 12
+// MFMAs per wave at ~2 blocks/CU, so a loop that drains its one prefetched
+// step before every barrier (the register kernel, and the earlier 2-buffer
+// DMA form whose __syncthreads() forced vmcnt(0)) waits out a full L2
+// latency per step. Here a step is
+//     s_waitcnt vmcnt(3*(NST-2))  -- retires only the OLDEST stage's DMA
+//     s_waitcnt lgkmcnt(0); s_barrier   (raw: no vmcnt(0) fence)
+//     DMA of step it+NST-1 into the stage step it-1 just finished reading
+//     ds_read_tr + 12 MFMA of step it
+// The DMA is issued from inline asm, so hipcc neither counts it nor drains
+// it ahead of the ds_reads; every wave issues exactly 3 DMA instructions per
+// stage (valid or zero-page sourced), which is what makes the count exact.
+// Stages are separate __shared__ objects addressed with literal indices
+// (the ds_read offsets fold to immediates); the loop runs full groups of
+// NST steps and the last <= 2*NST-2 steps are peeled after it, lowering
+// the wait count wave-uniformly to 0 (accumulators stay in place — a
+// mid-loop break made hipcc ping-pong them through a second AGPR set).
+//
+// The tr16 fragment reads use octet-swizzled positions;
+// sigma(row, oct) = oct ^ rho(row) with
 // rho(e) = (((e>>1)&1) + ((e>>3)&1)*2) << 1 spreads every {C+j, C+8+j}
 // 4-row read window over disjoint 8-dword bank blocks (the involution is
 // folded into the SOURCE granule, so DMA stays lane-linear). Invalid
-// pixels source the zero page. TK = 64 only.
+// pixels source the zero page. TK = 64 only. Same split / ipr chunking /
+// per-accumulator step order as conv_wgrad_row_kernel: slabs are
+// bit-identical to it.
 __device__ __forceinline__ int wrho(int e) {
     return (((e >> 1) & 1) + ((e >> 3) & 1) * 2) << 1;
 }
 
-template <bool AL>
-__global__ __launch_bounds__(256) void conv_wgrad_row_glds_kernel(
+#define WG_RING_NST 4                   // 48 KiB LDS: 3 blocks/CU
+
+struct WgRingStage {                    // one ring stage, 12 KiB
+    unsigned short A[32][64];           // dout: 32 pixel rows x 64 k
+    unsigned short B[64][64];           // in: 64 halo rows (>= worst 48)
+};
+
+// Three 16-B LDS-DMA pieces (1 KiB per wave each) to wave-uniform LDS byte
+// addresses l0..l2. M0 carries the LDS base and is the compiler's to keep,
+// so it is saved and restored inside the one statement.
+__device__ __forceinline__ void wg_ring_dma3(
+    const void* g0, const void* g1, const void* g2,
+    unsigned l0, unsigned l1, unsigned l2)
+{
+    unsigned keep;
+    asm volatile(
+        "s_mov_b32 %0, m0\n\t"
+        "s_mov_b32 m0, %4\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
+        "s_mov_b32 m0, %5\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\t"
+        "s_mov_b32 m0, %6\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, off\n\t"
+        "s_mov_b32 m0, %0"
+        : "=&s"(keep)
+        : "v"(g0), "v"(g1), "v"(g2), "s"(l0), "s"(l1), "s"(l2)
+        : "memory");
+}
+
+// Retire all but the newest N of this wave's DMA instructions, finish its
+// LDS reads, then meet the block — no vmcnt(0) unless N == 0.
+template <int N>
+__device__ __forceinline__ void wg_ring_sync() {
+    asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier"
+                 :: "i"(N) : "memory");
+}
+
+template <int NST>
+__global__ __launch_bounds__(256) void conv_wgrad_row_ring_kernel(
     const unsigned short* __restrict__ dout,  // [Nb,P,Q,K]
     const unsigned short* __restrict__ in,    // [Nb,H,W,C]
     float* __restrict__ partial,              // [SPLIT][K][9*C]
@@ -1390,18 +1464,17 @@ __global__ __launch_bounds__(256) void conv_wgrad_row_glds_kernel(
     int Nb, int H, int W, int C, int K, int P, int Q,
     int split, int ipr, int l2q, int l2p, int per_xcd)
 {
+    static_assert(NST == 3 || NST == 4, "ring depth");
     constexpr int TK = 64;
     constexpr int PAD = 1;
+    constexpr int DPS = 3;              // DMA instructions per wave per stage
     const int ROWS = 32 >> l2q;
     const int HW2 = W + 2;
-    // linear images: A 32 pixel-rows, B 64 halo rows (>= worst nbq=40;
-    // over-staged rows are zero-page sourced and never read)
-    __shared__ __attribute__((aligned(16))) struct {
-        unsigned short A[2][32][64];
-        unsigned short B[2][64][64];
-    } lds;
-    constexpr unsigned A1 = sizeof(lds.A[0]);
-    constexpr unsigned BB1 = sizeof(lds.B[0]);
+    // over-staged B rows are zero-page sourced and never read
+    __shared__ __attribute__((aligned(16))) WgRingStage sg0, sg1, sg2, sg3;
+    auto stg = [&](int st) -> WgRingStage* {    // literal st only
+        return st == 0 ? &sg0 : st == 1 ? &sg1 : st == 2 ? &sg2 : &sg3;
+    };
     constexpr int MI = TK / 32;
     const int tiles_k = (K + TK - 1) / TK;
     const int tiles_c = (C + 63) >> 6;
@@ -1436,55 +1509,57 @@ __global__ __launch_bounds__(256) void conv_wgrad_row_glds_kernel(
     // A: wave w stages pixels w*8 + (lane>>3), octet (lane&7) ^ rho(pixel)
     const int apix = wid * 8 + (lane >> 3);
     const int aoct = ((lane & 7) ^ wrho(apix));
-    const unsigned short* pdout = dout + (row0 << l2q) * K + k0
-                                  + (long)apix * K + aoct * 8;
+    // block-uniform running bases + per-lane constant element offsets
+    const unsigned short* pdout = dout + (row0 << l2q) * K + k0;
+    const int a_off = apix * K + aoct * 8;
+    const int a_row = apix >> l2q;
     // B: wave w stages halo rows {w*16 + j*8 + (lane>>3) : j 0..1}
     const long inrow0 = row0 + r - PAD;
     const unsigned short* pin0 = in + inrow0 * W * C + c0;
-    int b_rib[2], b_w[2], b_oct[2];
+    int b_rib[2], b_off[2];
     bool b_wok[2];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         int hp = wid * 16 + j * 8 + (lane >> 3);
-        b_oct[j] = ((lane & 7) ^ wrho(hp));
+        int oct = ((lane & 7) ^ wrho(hp));
         b_rib[j] = hp / HW2;            // halo row -> (in-row, w-1)
         int wpx = hp - b_rib[j] * HW2 - 1;
         b_wok[j] = wpx >= 0 && wpx < W && hp < ROWS * HW2;
-        b_w[j] = wpx < 0 ? 0 : wpx;
+        b_off[j] = (b_rib[j] * W + (wpx < 0 ? 0 : wpx)) * C + oct * 8;
     }
     long prow = row0;
 
-    auto glds_stage = [&](int buf) {
-        {   // A: one 1-KiB piece per wave
-            bool ok = (prow + (apix >> l2q)) < rows_total && apix < 32;
-            const unsigned short* gsrc = ok ? pdout : zpage;
-            __builtin_amdgcn_global_load_lds(
-                (const __attribute__((address_space(1))) void*)gsrc,
-                (__attribute__((address_space(3))) void*)
-                    &lds.A[buf][wid * 8][0], 16, 0, 0);
-        }
+    // wave-uniform LDS byte offsets of this wave's pieces within a stage
+    const unsigned wu = (unsigned)__builtin_amdgcn_readfirstlane(wid);
+    const unsigned ldA = wu * (8 * 128);
+    const unsigned ldB = (unsigned)sizeof(sg0.A) + wu * (16 * 128);
+
+    auto dma_stage = [&](int st) {      // literal st only
+        const unsigned sb = (unsigned)(unsigned long)
+            (__attribute__((address_space(3))) void*)stg(st);
+        const unsigned short* gs[DPS];
+        // rows of this step that exist at all (<= 8 are ever asked for)
+        const long rl = rows_total - prow;
+        const int rleft = rl < 64 ? (int)rl : 64;
+        const int pl = (int)prow;       // low bits suffice under & (P-1)
+        // A: one 1-KiB piece per wave
+        gs[0] = a_row < rleft ? pdout + a_off : zpage;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {   // B: two pieces per wave
-            int rib = b_rib[j];
-            int p = (int)((prow + rib) & (P - 1));
-            int h = p + r - PAD;
-            bool ok = b_wok[j] && h >= 0 && h < H
-                      && (prow + rib) < rows_total;
-            const unsigned short* gsrc = ok
-                ? pin0 + ((long)rib * W + b_w[j]) * C + b_oct[j] * 8
-                : zpage;
-            __builtin_amdgcn_global_load_lds(
-                (const __attribute__((address_space(1))) void*)gsrc,
-                (__attribute__((address_space(3))) void*)
-                    &lds.B[buf][wid * 16 + j * 8][0], 16, 0, 0);
+            int h = ((pl + b_rib[j]) & (P - 1)) + r - PAD;
+            bool ok = b_wok[j] & ((unsigned)h < (unsigned)H)
+                      & (b_rib[j] < rleft);
+            gs[1 + j] = ok ? pin0 + b_off[j] : zpage;
         }
+        wg_ring_dma3(gs[0], gs[1], gs[2],
+                     sb + ldA, sb + ldB, sb + ldB + 8 * 128);
         pdout += (long)32 * K;
         pin0 += (long)ROWS * W * C;
         prow += ROWS;
     };
 
     // ---- tr16 read offsets (octet-swizzled linear image) ----
-    const char* lb0 = (const char*)&lds;
+    const char* lb0 = (const char*)&sg0;
     unsigned roA[MI][2];
     unsigned roB[3][2][2];
 #pragma unroll
@@ -1494,7 +1569,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_row_glds_kernel(
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi) {
             int o = (wm * MI + mi) * 2 + (qd >> 1);
-            roA[mi][i] = (unsigned)((char*)&lds.A[0][e]
+            roA[mi][i] = (unsigned)((char*)&sg0.A[e]
                              [(o ^ wrho(e)) * 8 + (qd & 1) * 4] - lb0);
         }
         int rib = e >> l2q, q = e & (Q - 1);
@@ -1504,21 +1579,22 @@ __global__ __launch_bounds__(256) void conv_wgrad_row_glds_kernel(
 #pragma unroll
             for (int nj = 0; nj < 2; ++nj) {
                 int o = (wn * 2 + nj) * 2 + (qd >> 1);
-                roB[si][nj][i] = (unsigned)((char*)&lds.B[0][hp]
+                roB[si][nj][i] = (unsigned)((char*)&sg0.B[hp]
                                  [(o ^ wrho(hp)) * 8 + (qd & 1) * 4] - lb0);
             }
         }
     }
 
     union U64x8 { bf16x4_t h[2]; bf16x8_t v; };
-    auto mfma_step = [&](int buf) {
+    auto mfma_step = [&](int st) {      // literal st only
+        const char* sbp = (const char*)stg(st);
         U64x8 a[MI];
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi) {
             a[mi].h[0] = ds_tr16p((const unsigned short*)
-                (lb0 + roA[mi][0] + (buf ? A1 : 0)));
+                (sbp + roA[mi][0]));
             a[mi].h[1] = ds_tr16p((const unsigned short*)
-                (lb0 + roA[mi][1] + (buf ? A1 : 0)));
+                (sbp + roA[mi][1]));
         }
 #pragma unroll
         for (int si = 0; si < 3; ++si) {
@@ -1526,9 +1602,9 @@ __global__ __launch_bounds__(256) void conv_wgrad_row_glds_kernel(
 #pragma unroll
             for (int nj = 0; nj < 2; ++nj) {
                 bf[nj].h[0] = ds_tr16p((const unsigned short*)
-                    (lb0 + roB[si][nj][0] + (buf ? BB1 : 0)));
+                    (sbp + roB[si][nj][0]));
                 bf[nj].h[1] = ds_tr16p((const unsigned short*)
-                    (lb0 + roB[si][nj][1] + (buf ? BB1 : 0)));
+                    (sbp + roB[si][nj][1]));
             }
 #pragma unroll
             for (int mi = 0; mi < MI; ++mi)
@@ -1539,13 +1615,40 @@ __global__ __launch_bounds__(256) void conv_wgrad_row_glds_kernel(
         }
     };
 
-    glds_stage(0);
-    __syncthreads();
-    for (int it = 0; it < nsteps; ++it) {
-        if (it + 1 < nsteps)
-            glds_stage((it + 1) & 1);
-        mfma_step(it & 1);
-        __syncthreads();
+    // wait so that `ahead` stages stay in flight, then barrier
+    auto ring_sync = [&](int ahead) {
+        if (NST > 3 && ahead >= 2) wg_ring_sync<2 * DPS>();
+        else if (ahead >= 1)       wg_ring_sync<DPS>();
+        else                       wg_ring_sync<0>();
+    };
+
+    // prologue: up to NST-1 stages in flight (fewer for short blocks)
+#pragma unroll
+    for (int j = 0; j < NST - 1; ++j)
+        if (j < nsteps) dma_stage(j);
+    // steady state: full groups of NST steps, each of which still has a
+    // step NST-1 ahead of it to issue; the wait count is the constant
+    // DPS*(NST-2) and never 0
+    int it = 0;
+    for (; it + 2 * NST - 2 < nsteps; it += NST) {
+#pragma unroll
+        for (int j = 0; j < NST; ++j) {
+            ring_sync(NST - 2);
+            dma_stage((j + NST - 1) % NST);
+            mfma_step(j);
+        }
+    }
+    // peeled tail: the last rem <= 2*NST-2 steps (it % NST == 0, so step
+    // it+j reads stage j % NST); the stages left in flight run down to 0
+    const int rem = nsteps - it;
+#pragma unroll
+    for (int j = 0; j < 2 * NST - 2; ++j) {
+        if (j < rem) {
+            const int left = rem - 1 - j;
+            ring_sync(left < NST - 2 ? left : NST - 2);
+            if (j + NST - 1 < rem) dma_stage((j + NST - 1) % NST);
+            mfma_step(j % NST);
+        }
     }
 
     const int RSC = 9 * C;
@@ -2226,6 +2329,74 @@ static inline int ilog2_exact(long v) {
     return ((1L << l) == v) ? l : -1;
 }
 
+// Row-halo wgrad family (3x3 stride 1 pad 1 is the caller's to check; it
+// shows here as P == H, Q == W). variant 0 = register kernel, 1 = ring.
+// Q >= 4: a step stages ROWS * (Q + 2) = 32 + 64/Q halo pixels and the
+// register kernel's LDS B image holds 48 — at Q = 2 (VGG's last conv
+// stage) the writes ran past their c-subtile into the next one, a write
+// race: wrong and run-to-run different dw. Those shapes take the generic
+// kernel. The ring stages unconditional 16-B pieces: aligned channel / K
+// counts only.
+static bool wgrad_row_eligible(int H, int W, int C, int K, int P, int Q,
+                               int variant)
+{
+    if (P != H || Q != W || ilog2_exact(Q) < 0 || ilog2_exact(P) < 0
+        || Q < 4 || Q > 32)
+        return false;
+    if (variant == 1) return (C & 63) == 0 && (K & 63) == 0;
+    return variant == 0;
+}
+
+// Launches the chosen row kernel only (no slab reduce).
+static void launch_wgrad_row(
+    const void* dout, const void* in, void* partial_f32,
+    int Nb, int H, int W, int C, int K, int P, int Q, int split,
+    int variant, void* strm)
+{
+    const int TKr = 64;     // TK=128 acc pressure costs a wave/SIMD
+    int l2q_ = ilog2_exact(Q);
+    int tkr = (K + TKr - 1) / TKr, tcr = (C + 63) / 64;
+    long rows_total = (long)Nb * P;
+    int ROWS = 32 >> l2q_;
+    long ipr_l = (rows_total + split - 1) / split;
+    ipr_l = ((ipr_l + ROWS - 1) / ROWS) * ROWS;
+    long nlog = (long)tkr * tcr * 3 * split;
+    int pxc = (int)((nlog + 7) / 8);
+    long grid_r = (long)pxc * 8;
+    bool alr = ((C & 63) == 0) && (K % TKr == 0);
+#define WGR(TKV, ALV)                                                         \
+    hipLaunchKernelGGL((conv_wgrad_row_kernel<TKV, ALV>),                     \
+        dim3((unsigned)grid_r), dim3(256), 0, (hipStream_t)strm,              \
+        (const unsigned short*)dout, (const unsigned short*)in,               \
+        (float*)partial_f32, Nb, H, W, C, K, P, Q,                            \
+        split, (int)ipr_l, l2q_, 0, pxc)
+    if (variant == 1)
+        hipLaunchKernelGGL((conv_wgrad_row_ring_kernel<WG_RING_NST>),
+            dim3((unsigned)grid_r), dim3(256), 0, (hipStream_t)strm,
+            (const unsigned short*)dout, (const unsigned short*)in,
+            (float*)partial_f32, zpage_ptr(), Nb, H, W, C, K, P, Q,
+            split, (int)ipr_l, l2q_, 0, pxc);
+    else if (alr) WGR(64, true);
+    else          WGR(64, false);
+#undef WGR
+}
+
+// Test hook: one row-halo kernel alone into partial[split][K][9*C], so one
+// process can compare the two variants' slabs. Returns nonzero and launches
+// nothing for a shape the variant does not take.
+extern "C" int ps_conv_wgrad_row_variant(
+    const void* dout, const void* in, void* partial_f32,
+    int Nb, int H, int W, int C, int K, int P, int Q, int split,
+    int variant, void* strm)
+{
+    if (split < 1 || Nb < 1
+        || !wgrad_row_eligible(H, W, C, K, P, Q, variant))
+        return 1;
+    launch_wgrad_row(dout, in, partial_f32, Nb, H, W, C, K, P, Q, split,
+                     variant, strm);
+    return 0;
+}
+
 extern "C" void ps_conv_wgrad(
     const void* dout, const void* in, void* partial_f32, void* dw,
     int Nb, int H, int W, int C, int K, int P, int Q,
@@ -2273,49 +2444,19 @@ extern "C" void ps_conv_wgrad(
     {
         static int row_en = -1;
         if (row_en < 0) row_en = getenv("PS_WG_ROW_OFF") ? 0 : 1;
-        int l2q_ = ilog2_exact(Q), l2pq_ = ilog2_exact((long)P * Q);
-        // Q >= 4: a step stages ROWS * (Q + 2) = 32 + 64/Q halo pixels and
-        // the kernels' LDS B image holds 48 — at Q = 2 (VGG's last conv
-        // stage) the writes ran past their c-subtile into the next one, a
-        // write race: wrong and run-to-run different dw. Those shapes take
-        // the generic kernel.
-        if (row_en && stride == 1 && R == 3 && S == 3 && pad == 1 && P == H
-            && Q == W && l2q_ >= 0 && l2pq_ >= 0 && Q >= 4 && Q <= 32) {
-            static int wg_glds = -1;
-            if (wg_glds < 0) {
-                const char* e = getenv("PS_WG_GLDS");
-                wg_glds = e ? atoi(e) : 0;
+        if (row_en && stride == 1 && R == 3 && S == 3 && pad == 1
+            && wgrad_row_eligible(H, W, C, K, P, Q, 0)) {
+            // PS_WG_RING=0 returns the aligned shapes to the register
+            // kernel (A/B); ragged shapes always take it
+            static int wg_ring = -1;
+            if (wg_ring < 0) {
+                const char* e = getenv("PS_WG_RING");
+                wg_ring = e ? atoi(e) : 1;
             }
-            const int TKr = 64;     // TK=128 acc pressure costs a wave/SIMD
-            int tkr = (K + TKr - 1) / TKr, tcr = (C + 63) / 64;
-            long rows_total = (long)Nb * P;
-            int ROWS = 32 >> l2q_;
-            long ipr_l = (rows_total + split - 1) / split;
-            ipr_l = ((ipr_l + ROWS - 1) / ROWS) * ROWS;
-            long nlog = (long)tkr * tcr * 3 * split;
-            int pxc = (int)((nlog + 7) / 8);
-            long grid_r = (long)pxc * 8;
-            bool alr = ((C & 63) == 0) && (K % TKr == 0);
-#define WGR(TKV, ALV)                                                         \
-            hipLaunchKernelGGL((conv_wgrad_row_kernel<TKV, ALV>),             \
-                dim3((unsigned)grid_r), dim3(256), 0, (hipStream_t)strm,      \
-                (const unsigned short*)dout, (const unsigned short*)in,       \
-                (float*)partial_f32, Nb, H, W, C, K, P, Q,                    \
-                split, (int)ipr_l, l2q_, 0, pxc)
-#define WGRG(ALV)                                                             \
-            hipLaunchKernelGGL((conv_wgrad_row_glds_kernel<ALV>),             \
-                dim3((unsigned)grid_r), dim3(256), 0, (hipStream_t)strm,      \
-                (const unsigned short*)dout, (const unsigned short*)in,       \
-                (float*)partial_f32, zpage_ptr(), Nb, H, W, C, K, P, Q,       \
-                split, (int)ipr_l, l2q_, 0, pxc)
-            // GLDS form stages unconditional 16-B pieces: aligned
-            // channel/K counts only (alr); ragged shapes keep the
-            // register-staged kernel
-            if (wg_glds && alr) WGRG(true);
-            else if (alr)       WGR(64, true);
-            else                WGR(64, false);
-#undef WGRG
-#undef WGR
+            int variant = (wg_ring
+                           && wgrad_row_eligible(H, W, C, K, P, Q, 1)) ? 1 : 0;
+            launch_wgrad_row(dout, in, partial_f32, Nb, H, W, C, K, P, Q,
+                             split, variant, strm);
             long n_ = (long)K * 9 * C;
             launch_reduce_slabs((unsigned short*)dw, (float*)partial_f32, n_,
                                 split, (hipStream_t)strm);
