@@ -101,6 +101,13 @@ def _try_load() -> None:
         lib.ps_conv_wgrad_row_variant.argtypes = [ctypes.c_void_p] * 3 + [
             ctypes.c_int] * 9 + [ctypes.c_void_p]
         lib.ps_conv_wgrad_row_variant.restype = ctypes.c_int
+        # test hook: dgrad (0 fwd, 1 dgrad), src, wgt (dgrad: wT), bias,
+        # dst, carry, Nb, H, W, C, K, P, Q, variant (0 generic GEMM kernel,
+        # 1 halo-resident 3x3 kernel), stream; one launch alone; nonzero =
+        # not a shape the halo kernel takes, nothing launched
+        lib.ps_conv_halo_variant.argtypes = [ctypes.c_int] + [
+            ctypes.c_void_p] * 5 + [ctypes.c_int] * 8 + [ctypes.c_void_p]
+        lib.ps_conv_halo_variant.restype = ctypes.c_int
         lib.ps_conv_bias_grad.argtypes = [ctypes.c_void_p] * 3 + [
             ctypes.c_long, ctypes.c_int, ctypes.c_void_p]
         lib.ps_wt_transpose.argtypes = [ctypes.c_void_p, ctypes.c_void_p,

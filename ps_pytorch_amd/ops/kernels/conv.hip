@@ -26,6 +26,10 @@
 //     while the loads fly. Staging addresses are affine-walked (per-row
 //     running pointers + wave-uniform step deltas + precomputed tap-validity
 //     bitmasks) — a per-step address rebuild made the kernels VALU-bound.
+//   * 64 -> 64 3x3 s1 p1 fwd/dgrad (ResNet layer 1) take
+//     conv3x3_halo_kernel: the block's halo patch is loaded once instead
+//     of once per tap, weights stream through a 3-stage LDS ring
+//     (PS_CONV_HALO=0: A/B against the generic kernel, bit-identical).
 //   * stride is a template parameter; stride-2 dgrad runs by PARITY CLASS
 //     (conv_dgrad2_kernel, one launch for all four classes) at full tile
 //     density instead of predicating 3/4 of the MFMAs to zero.
@@ -655,6 +659,243 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(
             }
         }
     }
+    }
+}
+
+// ------------------------------------- fwd / dgrad, 3x3 s1 p1, 64 -> 64
+//
+// conv_gemm_kernel<128,64> stages a fresh 128x64 A tile per tap, although
+// the nine tiles of a block are one (128/W + 2) x (W + 2) pixel halo patch
+// read at nine shifts: 9x the L2->LDS traffic the block needs, one step in
+// flight, a vmcnt(0) per barrier. conv3x3_halo_kernel loads the patch ONCE
+// (LDS-DMA, 1-KiB pieces of 8 pixels x 128 B, PW pieces per wave, piece i
+// issued by wave i % 4) and streams only the 8-KiB B slice of each tap
+// through a 3-stage ring with the wgrad ring's recipe: DMA from inline asm
+// (hipcc neither counts nor drains it), counted vmcnt + lgkmcnt(0) + raw
+// s_barrier per tap, a stage read one barrier after the wait that retires
+// it and restaged one barrier after its last read. The nine taps are
+// unrolled; issue order is B0, A[0..4], B1, A[5..], B2, then B(t+2) in tap
+// t, so the waits run PW-1, PW-3, 2, 2, 2, 2, 2, 2, 0 pieces outstanding.
+// The r = 0 taps need only the first 128/W + 1 patch rows (5 pieces per
+// wave; dgrad reads the patch bottom-up, so it is issued bottom-up).
+//
+// LDS pixel lp = hr * (W + 2) + hc holds input pixel (h0 - 1 + hr, hc - 1);
+// outside the image (and past the patch) the source is the zero page.
+// fwd tap (r,s) of output (py,px) reads lp = (py + r)(W + 2) + px + s,
+// dgrad reads (py + 2 - r)(W + 2) + px + 2 - s. Position p of LDS row lp
+// holds granule p ^ (((lp >> 1) & 3) << 1) (gswz mode 2 keyed on lp, folded
+// into the source address). A fragment read covers 16 CONSECUTIVE lp from
+// any base, even or odd: each ds_read_b128 lane group takes rows
+// base + {0-3, 12-15} at granule g and base + {4-11} at g ^ 1, and in both
+// sets (lp & 1, (lp >> 1) & 3) runs through all 8 values exactly once for
+// every base, so the 16 lanes hit the 16 distinct 16-B bank classes.
+//
+// Same MFMA, same lane layout, taps in (r,s) order and kk = 0, 1 within a
+// tap, same f32 bias / carry add and single rounding as conv_gemm_kernel:
+// outputs are bit-identical to it.
+template <int W>
+struct HaloLds {
+    static constexpr int RT = 128 / W;              // image rows per tile
+    static constexpr int HW2 = W + 2;
+    static constexpr int NPIX = (RT + 2) * HW2;     // patch pixels
+    static constexpr int PW = (NPIX + 31) / 32;     // A pieces per wave
+    unsigned short A[PW * 32][64];
+    unsigned short B[3][64][64];
+};
+
+// 16-B LDS-DMA pieces (1 KiB per wave each) to wave-uniform LDS byte
+// addresses; M0 is saved and restored inside the one statement.
+__device__ __forceinline__ void halo_dma1(const void* g0, unsigned l0)
+{
+    unsigned keep;
+    asm volatile(
+        "s_mov_b32 %0, m0\n\t"
+        "s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
+        "s_mov_b32 m0, %0"
+        : "=&s"(keep) : "v"(g0), "s"(l0) : "memory");
+}
+
+__device__ __forceinline__ void halo_dma2(
+    const void* g0, const void* g1, unsigned l0, unsigned l1)
+{
+    unsigned keep;
+    asm volatile(
+        "s_mov_b32 %0, m0\n\t"
+        "s_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
+        "s_mov_b32 m0, %4\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\t"
+        "s_mov_b32 m0, %0"
+        : "=&s"(keep) : "v"(g0), "v"(g1), "s"(l0), "s"(l1) : "memory");
+}
+
+// Retire all but the newest N of this wave's DMA instructions, finish its
+// LDS reads, then meet the block — no vmcnt(0) unless N == 0. (Shared with
+// the wgrad ring below.)
+template <int N>
+__device__ __forceinline__ void lds_ring_sync() {
+    asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier"
+                 :: "i"(N) : "memory");
+}
+
+template <int W, bool DGRAD, bool ACCF>
+__global__ __launch_bounds__(256) void conv3x3_halo_kernel(
+    const unsigned short* __restrict__ src,  // fwd: in; dgrad: dout [Nb,H,W,64]
+    const unsigned short* __restrict__ wgt,  // fwd: w [64,3,3,64]; dgrad: wT [3,3,64,64]
+    const unsigned short* __restrict__ bias, // [64] or null (fwd only)
+    unsigned short* __restrict__ dst,        // [Nb,H,W,64]
+    const unsigned short* __restrict__ carry,// [dst shape] (ACCF)
+    const unsigned short* __restrict__ zpage,
+    int H)
+{
+    using L = HaloLds<W>;
+    constexpr int RT = L::RT, HW2 = L::HW2, NPIX = L::NPIX, PW = L::PW;
+    constexpr int J0 = 5;       // pieces per wave the r = 0 taps need
+    // the r = 0 taps read lp < RT * HW2 (fwd) or lp >= 2 * HW2 (dgrad, whose
+    // pieces run from the top of the image down): inside the first 4 * J0
+    static_assert(RT * HW2 <= 32 * J0 && 32 * PW - 2 * HW2 <= 32 * J0
+                  && J0 <= PW, "early-start piece count");
+    static_assert(sizeof(L) >= 128 * 64 * 4, "f32 staging fits LDS");
+    __shared__ __attribute__((aligned(128))) L lds;
+
+    const int t = threadIdx.x;
+    const int lane = t & 63, wid = t >> 6;
+    const int wm = wid >> 1, wn = wid & 1;
+    const int fr = lane & 15, fq = lane >> 4;
+    const int tpi = H / RT;                     // tiles per image
+    const int n = blockIdx.x / tpi;
+    const int h0 = (blockIdx.x - n * tpi) * RT;
+    const long m0 = (long)blockIdx.x * 128;
+    const unsigned short* img = src + (long)n * H * W * 64;
+
+    const int wu = __builtin_amdgcn_readfirstlane(wid);
+    const unsigned ldsA = (unsigned)(unsigned long)
+        (__attribute__((address_space(3))) void*)&lds.A[0][0];
+    const unsigned ldsB = (unsigned)(unsigned long)
+        (__attribute__((address_space(3))) void*)&lds.B[0][0][0];
+
+    // B: wave w stages rows (output columns) w*16 + rr*8 + (lane>>3)
+    const unsigned short* pB[2];
+#pragma unroll
+    for (int rr = 0; rr < 2; ++rr) {
+        int row = wid * 16 + rr * 8 + (lane >> 3);
+        pB[rr] = wgt + row * (DGRAD ? 64 : 9 * 64)
+                 + gswz<2>(row, lane & 7) * 8;
+    }
+    constexpr int BTAP = DGRAD ? 64 * 64 : 64;  // elements between taps
+    auto dma_b = [&](int tap) {                 // literal tap only
+        const unsigned l = ldsB + (tap % 3) * 8192 + wu * 2048;
+        halo_dma2(pB[0] + tap * BTAP, pB[1] + tap * BTAP, l, l + 1024);
+    };
+    auto dma_a = [&](int j) {                   // literal j only
+        const int i = j * 4 + wu;
+        const int gi = DGRAD ? 4 * PW - 1 - i : i;
+        const int lp = gi * 8 + (lane >> 3);
+        const int hr = lp / HW2, hc = lp - hr * HW2;
+        const int h = h0 - 1 + hr, wc = hc - 1;
+        const bool ok = (lp < NPIX) & ((unsigned)h < (unsigned)H)
+                        & ((unsigned)wc < (unsigned)W);
+        const int off = (h * W + wc) * 64
+                        + (((lane & 7) ^ (((lp >> 1) & 3) << 1)) * 8);
+        const unsigned short* gs = ok ? img + off : zpage;
+        halo_dma1(gs, ldsA + gi * 1024);
+    };
+
+    f32x4_t acc[4][2];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
+
+    // patch pixel of this lane's output row mi*16 + fr at shift (0,0)
+    int lp0[4];
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi) {
+        int o = wm * 64 + mi * 16 + fr;
+        lp0[mi] = (o / W) * HW2 + (o % W);
+    }
+    int brow[2];
+#pragma unroll
+    for (int nj = 0; nj < 2; ++nj) brow[nj] = wn * 32 + nj * 16 + fr;
+
+    auto mfma_tap = [&](int tap) {              // literal tap only
+        const int r = tap / 3, s = tap % 3;
+        const int toff = DGRAD ? (2 - r) * HW2 + (2 - s) : r * HW2 + s;
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) {
+            bf16x8_t a[4], b[2];
+#pragma unroll
+            for (int mi = 0; mi < 4; ++mi) {
+                int lp = lp0[mi] + toff;
+                a[mi] = *(const bf16x8_t*)
+                    &lds.A[lp][((kk * 4 + fq) ^ (((lp >> 1) & 3) << 1)) * 8];
+            }
+#pragma unroll
+            for (int nj = 0; nj < 2; ++nj)
+                b[nj] = *(const bf16x8_t*)
+                    &lds.B[tap % 3][brow[nj]]
+                          [gswz<2>(brow[nj], kk * 4 + fq) * 8];
+#pragma unroll
+            for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+                for (int nj = 0; nj < 2; ++nj)
+                    acc[mi][nj] = MFMA_BF16(a[mi], b[nj], acc[mi][nj]);
+        }
+    };
+
+    dma_b(0);
+#pragma unroll
+    for (int j = 0; j < J0; ++j) dma_a(j);
+    dma_b(1);
+#pragma unroll
+    for (int j = J0; j < PW; ++j) dma_a(j);
+    dma_b(2);
+
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap) {
+        // retires: B0 + A[0..J0) | B1 | B(tap), and the rest of A by tap 2
+        if (tap == 0)      lds_ring_sync<PW - J0 + 4>();
+        else if (tap == 1) lds_ring_sync<PW - J0 + 2>();
+        else if (tap < 8)  lds_ring_sync<2>();
+        else               lds_ring_sync<0>();
+        if (tap >= 1 && tap + 2 < 9) dma_b(tap + 2);
+        mfma_tap(tap);
+    }
+    lds_ring_sync<0>();         // every wave done reading before the overlay
+
+    // ---- epilogue: conv_gemm_kernel's, at TM = 128, TN = Nout = 64 ----
+    float* sf = reinterpret_cast<float*>(&lds);
+#pragma unroll
+    for (int nj = 0; nj < 2; ++nj) {
+        int cl = wn * 32 + nj * 16 + fr;
+        float bv = (!DGRAD && bias) ? bf16_to_f32(bias[cl]) : 0.f;
+#pragma unroll
+        for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            sf[(wm * 64 + mi * 16 + fq * 4 + e) * 64 + cl]
+                = acc[mi][nj][e] + bv;
+    }
+    __syncthreads();
+    const int segc = (t & 7) * 8;
+    const int rl0 = t >> 3;
+#pragma unroll
+    for (int ps = 0; ps < 4; ++ps) {
+        int rl = ps * 32 + rl0;
+        long om = m0 + rl;
+        f32x4_t a0 = *(const f32x4_t*)&sf[rl * 64 + segc];
+        f32x4_t a1 = *(const f32x4_t*)&sf[rl * 64 + segc + 4];
+        float v[8];
+#pragma unroll
+        for (int k2 = 0; k2 < 4; ++k2) { v[k2] = a0[k2]; v[4 + k2] = a1[k2]; }
+        V16 o;
+        if constexpr (ACCF) {
+            V16 cv = *(const V16*)&carry[om * 64 + segc];
+#pragma unroll
+            for (int k2 = 0; k2 < 8; ++k2)
+                v[k2] += bf16_to_f32(cv.us[k2]);
+        }
+#pragma unroll
+        for (int k2 = 0; k2 < 8; ++k2) o.us[k2] = f32_to_bf16(v[k2]);
+        *(uint4*)&dst[om * 64 + segc] = o.u4;
     }
 }
 
@@ -1447,14 +1688,6 @@ __device__ __forceinline__ void wg_ring_dma3(
         : "memory");
 }
 
-// Retire all but the newest N of this wave's DMA instructions, finish its
-// LDS reads, then meet the block — no vmcnt(0) unless N == 0.
-template <int N>
-__device__ __forceinline__ void wg_ring_sync() {
-    asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier"
-                 :: "i"(N) : "memory");
-}
-
 template <int NST>
 __global__ __launch_bounds__(256) void conv_wgrad_row_ring_kernel(
     const unsigned short* __restrict__ dout,  // [Nb,P,Q,K]
@@ -1617,9 +1850,9 @@ __global__ __launch_bounds__(256) void conv_wgrad_row_ring_kernel(
 
     // wait so that `ahead` stages stay in flight, then barrier
     auto ring_sync = [&](int ahead) {
-        if (NST > 3 && ahead >= 2) wg_ring_sync<2 * DPS>();
-        else if (ahead >= 1)       wg_ring_sync<DPS>();
-        else                       wg_ring_sync<0>();
+        if (NST > 3 && ahead >= 2) lds_ring_sync<2 * DPS>();
+        else if (ahead >= 1)       lds_ring_sync<DPS>();
+        else                       lds_ring_sync<0>();
     };
 
     // prologue: up to NST-1 stages in flight (fewer for short blocks)
@@ -2191,7 +2424,7 @@ static const unsigned short* zpage_ptr() {
 // stats != null: the epilogue also writes per-channel sum/sumsq partials
 // [ceil(M/128)][2*K] for the following BatchNorm (generic NBUF=2 fwd paths
 // only — the python side mirrors the dispatch to know when to allocate).
-extern "C" void ps_conv_fwd(
+static void conv_fwd_generic(
     const void* src, const void* wgt, const void* bias, void* dst,
     void* stats,
     int Nb, int H, int W, int C, int K, int P, int Q,
@@ -2250,7 +2483,7 @@ extern "C" void ps_conv_fwd(
 // carry != null fuses a same-shaped bf16 tensor into the dx epilogue
 // (dx = dgrad + carry): the residual-fork gradient accumulation that
 // autograd otherwise runs as a separate elementwise add.
-extern "C" void ps_conv_dgrad(
+static void conv_dgrad_generic(
     const void* src, const void* wgt, void* dst, const void* carry,
     int Nb, int H, int W, int C, int K, int P, int Q,
     int R, int S, int stride, int pad, void* strm)
@@ -2322,6 +2555,103 @@ extern "C" void ps_conv_dgrad(
                   else          DG2(128, 64, false); }
 #undef DG2
     }
+}
+
+// PS_CONV_HALO=0 returns the 64 -> 64 3x3 shapes to conv_gemm_kernel (A/B).
+static inline int halo_mode() {
+    static int m = -1;
+    if (m < 0) { const char* e = getenv("PS_CONV_HALO"); m = e ? atoi(e) : 1; }
+    return m;
+}
+
+// Shapes conv3x3_halo_kernel takes: 3x3 stride 1 pad 1 (so P == H, Q == W),
+// 64 contraction channels and 64 output columns, a 128-pixel tile that is
+// 128 / W whole rows of ONE image (no ragged M tile), no BN-stats epilogue.
+static bool conv_halo_eligible(int H, int W, int C, int K, int P, int Q,
+                               int R, int S, int stride, int pad,
+                               const void* stats)
+{
+    return R == 3 && S == 3 && stride == 1 && pad == 1 && P == H && Q == W
+        && C == 64 && K == 64 && (W == 16 || W == 32) && H > 0
+        && H % (128 / W) == 0 && stats == nullptr;
+}
+
+static void launch_conv_halo(
+    bool dgrad, const void* src, const void* wgt, const void* bias,
+    void* dst, const void* carry, int Nb, int H, int W, void* strm)
+{
+    const long grid = (long)Nb * H * W / 128;
+#define HALO(WV, DG, ACV)                                                     \
+    hipLaunchKernelGGL((conv3x3_halo_kernel<WV, DG, ACV>),                    \
+        dim3((unsigned)grid), dim3(256), 0, (hipStream_t)strm,                \
+        (const unsigned short*)src, (const unsigned short*)wgt,               \
+        (const unsigned short*)bias, (unsigned short*)dst,                    \
+        (const unsigned short*)carry, zpage_ptr(), H)
+#define HALO_W(DG, ACV) do { if (W == 32) HALO(32, DG, ACV);                  \
+                             else         HALO(16, DG, ACV); } while (0)
+    if (!dgrad)     HALO_W(false, false);
+    else if (carry) HALO_W(true, true);
+    else            HALO_W(true, false);
+#undef HALO_W
+#undef HALO
+}
+
+// The halo kernel stands in for the default GLDS / mode-2 generic kernel
+// only, so PS_GLDS=0 and PS_SWZ=1 keep selecting what they always did.
+static inline bool halo_on() {
+    return halo_mode() && glds_mode() && swz_mode() == 2;
+}
+
+extern "C" void ps_conv_fwd(
+    const void* src, const void* wgt, const void* bias, void* dst,
+    void* stats,
+    int Nb, int H, int W, int C, int K, int P, int Q,
+    int R, int S, int stride, int pad, void* strm)
+{
+    if (halo_on()
+        && conv_halo_eligible(H, W, C, K, P, Q, R, S, stride, pad, stats))
+        launch_conv_halo(false, src, wgt, bias, dst, nullptr, Nb, H, W, strm);
+    else
+        conv_fwd_generic(src, wgt, bias, dst, stats, Nb, H, W, C, K, P, Q,
+                         R, S, stride, pad, strm);
+}
+
+extern "C" void ps_conv_dgrad(
+    const void* src, const void* wgt, void* dst, const void* carry,
+    int Nb, int H, int W, int C, int K, int P, int Q,
+    int R, int S, int stride, int pad, void* strm)
+{
+    if (halo_on()
+        && conv_halo_eligible(H, W, C, K, P, Q, R, S, stride, pad, nullptr))
+        launch_conv_halo(true, src, wgt, nullptr, dst, carry, Nb, H, W, strm);
+    else
+        conv_dgrad_generic(src, wgt, dst, carry, Nb, H, W, C, K, P, Q,
+                           R, S, stride, pad, strm);
+}
+
+// Test hook: one 3x3 s1 p1 fwd (dgrad = 0) or dgrad launch alone, so one
+// process can compare the kernels. variant 0 = the conv_gemm_kernel the
+// generic dispatch picks, 1 = conv3x3_halo_kernel. Returns nonzero and
+// launches nothing for a shape the halo kernel does not take (P, Q are the
+// output dims the caller would pass to ps_conv_fwd / ps_conv_dgrad).
+extern "C" int ps_conv_halo_variant(
+    int dgrad, const void* src, const void* wgt, const void* bias,
+    void* dst, const void* carry,
+    int Nb, int H, int W, int C, int K, int P, int Q, int variant, void* strm)
+{
+    if (Nb < 1 || (variant != 0 && variant != 1)
+        || !conv_halo_eligible(H, W, C, K, P, Q, 3, 3, 1, 1, nullptr))
+        return 1;
+    if (variant == 1)
+        launch_conv_halo(dgrad != 0, src, wgt, dgrad ? nullptr : bias, dst,
+                         dgrad ? carry : nullptr, Nb, H, W, strm);
+    else if (dgrad)
+        conv_dgrad_generic(src, wgt, dst, carry, Nb, H, W, C, K, P, Q,
+                           3, 3, 1, 1, strm);
+    else
+        conv_fwd_generic(src, wgt, bias, dst, nullptr, Nb, H, W, C, K, P, Q,
+                         3, 3, 1, 1, strm);
+    return 0;
 }
 
 static inline int ilog2_exact(long v) {

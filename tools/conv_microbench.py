@@ -6,6 +6,8 @@ computes dgrad+wgrad together when both leaves require grad, which
 conflates the per-op numbers).
 
 Run on a GPU box:  python tools/conv_microbench.py [--batch 1024]
+                   [--only "l1 64->64"]   (one shape alone, e.g. under both
+                                           values of PS_CONV_HALO)
 """
 import argparse
 import sys
@@ -30,6 +32,8 @@ SHAPES = [
     ("l3 256->256", 256, 8, 8, 256, 3, 1, 1),
     ("l4d 256->512 s2", 256, 8, 8, 512, 3, 2, 1),
     ("l4 512->512", 512, 4, 4, 512, 3, 1, 1),
+    # not a ResNet-18 layer: the W = 16 shape conv3x3_halo_kernel also takes
+    ("w16 64->64", 64, 16, 16, 64, 3, 1, 1),
 ]
 
 
@@ -44,17 +48,31 @@ def timeit(fn, iters=20, warmup=5):
     return (time.time() - t0) / iters * 1e6   # us
 
 
+def select_shapes(only):
+    """SHAPES, or the entries named in `only` (a typo is an error)."""
+    if not only:
+        return SHAPES
+    names = [s[0] for s in SHAPES]
+    for o in only:
+        if o not in names:
+            raise SystemExit(f"--only {o!r}: no such shape; have {names}")
+    return [s for s in SHAPES if s[0] in only]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--batch', type=int, default=1024)
     ap.add_argument('--iters', type=int, default=20)
+    ap.add_argument('--only', action='append', default=None, metavar='NAME',
+                    help='time only the shape with this name (repeatable)')
     args = ap.parse_args()
+    shapes = select_shapes(args.only)
     torch.backends.cudnn.benchmark = True
     lib = require_lib()
     Nb = args.batch
     print(f"{'shape':>20} {'impl':>6} {'fwd us':>9} {'dgrad us':>9} "
           f"{'wgrad us':>9} {'TF fwd':>7} {'TF dx':>7} {'TF dw':>7}")
-    for name, C, H, W, K, R, stride, pad in SHAPES:
+    for name, C, H, W, K, R, stride, pad in shapes:
         P = (H + 2 * pad - R) // stride + 1
         x = torch.randn(Nb, C, H, W, device='cuda', dtype=torch.bfloat16) \
             .contiguous(memory_format=_CL)
