@@ -19,7 +19,8 @@ SHAPES = [
     (8, 128, 16, 16, 128, 3, 1, 1, False),
     (8, 64, 32, 32, 128, 1, 2, 0, False),    # 1x1 s2 shortcut
     (4, 256, 8, 8, 512, 3, 2, 1, False),
-    (4, 3, 32, 32, 64, 3, 1, 1, False),      # stem C=3 (scalar path)
+    (4, 3, 32, 32, 64, 3, 1, 1, False),      # stem C=3 with an input grad
+                                             # (padded to C=8)
     (4, 1, 28, 28, 20, 5, 1, 0, True),       # LeNet conv1
     (4, 20, 12, 12, 50, 5, 1, 0, True),      # LeNet conv2 (C,K % 8 != 0)
     (3, 16, 9, 7, 24, 3, 1, 1, False),       # ragged M (tile tails)
