@@ -124,10 +124,38 @@ def add_fit_args(parser: argparse.ArgumentParser) -> argparse.ArgumentParser:
                              '(parameters only — the reference checkpoints '
                              'no optimizer state; 0 = fresh start)')
     parser.add_argument('--optimizer', type=str, default='sgd',
-                        help='PS-side optimizer: sgd | adam (the reference '
-                             'ships optim/adam.py but hardwires SGD at '
-                             'sync_replicas_master_nn.py:126 — here both '
-                             'fused flat optimizers are selectable)')
+                        help='PS-side optimizer: sgd | adam | lars (the '
+                             'reference ships optim/adam.py but hardwires SGD '
+                             'at sync_replicas_master_nn.py:126 — here the '
+                             'fused flat optimizers are selectable; lars = '
+                             'momentum SGD with a per-tensor trust ratio, '
+                             'the large-batch recipe, and the one optimizer '
+                             'whose --lr-schedule a captured step graph '
+                             'follows)')
+    parser.add_argument('--weight-decay', type=float, default=0.0,
+                        metavar='WD',
+                        help='L2 weight decay of the PS-side optimizer (lars '
+                             'exempts 1-D tensors: biases, BN affine)')
+    parser.add_argument('--lars-eta', type=float, default=1e-3, metavar='ETA',
+                        help='LARS trust coefficient: per tensor the step is '
+                             'lr * eta*|w| / (|g| + wd*|w|)')
+    parser.add_argument('--lr-schedule', type=str, default='constant',
+                        help='constant | step | poly | cosine over '
+                             '--max-steps, after --warmup-steps of linear '
+                             'warmup: step multiplies by --lr-decay-gamma '
+                             'every --lr-decay-steps, poly decays with power '
+                             '2 to zero, cosine is one half period. sgd and '
+                             'adam follow it on the eager paths only (their '
+                             'kernels take lr by value, so graph capture is '
+                             'refused); lars reads it on the device')
+    parser.add_argument('--warmup-steps', type=int, default=0, metavar='N',
+                        help='linear LR warmup from lr/N over the first N '
+                             'steps')
+    parser.add_argument('--lr-decay-steps', type=int, default=0, metavar='N',
+                        help='steps between decays of --lr-schedule step')
+    parser.add_argument('--lr-decay-gamma', type=float, default=0.1,
+                        metavar='G',
+                        help='decay factor of --lr-schedule step')
     parser.add_argument('--engine', type=str, default='ps',
                         help='ps (1 PS + N-1 workers, the reference design) | '
                              'allreduce (collective DP on all N ranks — the '
@@ -192,8 +220,31 @@ class JobConfig:
     compress_codec: str = 'q8'
     topk_k: int = 16
     fan_in: str = 'arrival'
+    weight_decay: float = 0.0
+    lars_eta: float = 1e-3
+    lr_schedule: str = 'constant'
+    warmup_steps: int = 0
+    lr_decay_steps: int = 0
+    lr_decay_gamma: float = 0.1
 
     def __post_init__(self) -> None:
+        if self.lr_schedule not in ('constant', 'step', 'poly', 'cosine'):
+            raise ValueError(f"unknown --lr-schedule {self.lr_schedule!r}")
+        if self.weight_decay < 0:
+            raise ValueError(f"--weight-decay must be >= 0, got "
+                             f"{self.weight_decay!r}")
+        if self.warmup_steps < 0:
+            raise ValueError(f"--warmup-steps must be >= 0, got "
+                             f"{self.warmup_steps!r}")
+        if self.lr_schedule == 'step' and self.lr_decay_steps < 1:
+            raise ValueError("--lr-schedule step needs --lr-decay-steps >= 1")
+        # a warmup as long as the run would leave the decay nothing to span
+        if self.warmup_steps >= max(self.max_steps, 1) and self.warmup_steps:
+            import warnings
+            warnings.warn(f"--warmup-steps {self.warmup_steps} covers all "
+                          f"--max-steps {self.max_steps}; clamping to "
+                          f"{max(self.max_steps, 1) - 1}")
+            self.warmup_steps = max(self.max_steps, 1) - 1
         if self.fan_in not in ('arrival', 'fused'):
             raise ValueError(f"unknown --fan-in {self.fan_in!r}")
         if self.compress_codec not in ('q8', 'topk'):
@@ -207,7 +258,7 @@ class JobConfig:
             raise ValueError(f"unknown --mode {self.mode!r}")
         if self.aggregation not in ('collective', 'gather'):
             raise ValueError(f"unknown --aggregation {self.aggregation!r}")
-        if self.optimizer not in ('sgd', 'adam'):
+        if self.optimizer not in ('sgd', 'adam', 'lars'):
             raise ValueError(f"unknown --optimizer {self.optimizer!r}")
         # --mode kill needs arrival-order fan-in: the PS's kill verdict fires
         # from the gather drain's first-k quota (parallel/ps.py); a collective

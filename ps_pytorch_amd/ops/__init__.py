@@ -115,6 +115,26 @@ def _try_load() -> None:
         lib.ps_fused_adam.argtypes = [ctypes.c_void_p] * 6 + [
             ctypes.c_long] + [ctypes.c_float] * 7 + [
             ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
+        # fused LARS (lars.hip). norms: w, g, g_dtype, chunk_start,
+        # chunk_len, chunk0, nchunk, seg_chunk0, seg_adapt, seg0, nseg,
+        # partial, seg_sums, local_lr, wd_seg, lr_table, T, step_ctr, lr_cur,
+        # advance, grad_scale, eta, wd, eps (f64), stream / update: w, g, m,
+        # wire, g_dtype, wire_dtype, chunk_start, chunk_seg, chunk0, nchunk,
+        # local_lr, wd_seg, mu, scale, stream; nonzero = rejected, no launch
+        lib.ps_lars_norms.argtypes = [
+            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+            ctypes.c_void_p, ctypes.c_int] + [ctypes.c_double] * 4 + [
+            ctypes.c_void_p]
+        lib.ps_lars_norms.restype = ctypes.c_int
+        lib.ps_lars_update.argtypes = [ctypes.c_void_p] * 4 + [
+            ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+            ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+            ctypes.c_float, ctypes.c_float, ctypes.c_void_p]
+        lib.ps_lars_update.restype = ctypes.c_int
         lib.ps_bn_fwd.argtypes = [ctypes.c_void_p] * 13 + [
             ctypes.c_int,
             ctypes.c_long, ctypes.c_long, ctypes.c_float, ctypes.c_float,

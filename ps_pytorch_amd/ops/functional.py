@@ -110,6 +110,231 @@ def fused_adam_step(
     if wire_out is not None:
         wire_out.copy_(w.to(wire_out.dtype))
 
+
+# ---- fused LARS (ops/kernels/lars.hip) ----
+# Per parameter tensor ("segment") of the flat layout: Sw = sum w^2 over the
+# f32 master weights and Sg = sum g^2 over the raw gradient sum, both in
+# float64; then in float64 wn = sqrt(Sw), gn = grad_scale * sqrt(Sg),
+#   ratio = eta*wn / (gn + wd*wn + eps)  if adapt and wn > 0 and gn > 0 else 1
+#   local_lr = f32(lr * ratio),  wd_seg = wd if adapt else 0
+# with adapt = ndim > 1 and lr = lr_table[min(step_ctr, T-1)], latched into
+# lr_cur (and step_ctr incremented) only by a call with advance=True. The
+# update is, per element in f32: g = s*scale (+ wd_seg*w, one fma);
+# m = fma(mu, m, local_lr*g); w = w - m; wire = cast(w). The CPU paths are
+# the numerics oracle: torch float64 sums, the scalar formula in Python
+# floats, the elementwise chain in f32 with fma taken through float64.
+
+LARS_CHUNK = 4096      # elements per chunk (LARS_CHUNK in lars.hip)
+LARS_ALIGN = 8         # segment starts: FlatSpace's ALIGN
+
+
+class LarsLayout:
+    """Chunk and segment tables of one flat layout plus the per-layout
+    workspaces, built once and kept on `device`.
+
+    segments: (offset, numel, ndim) per parameter in flat order, offsets
+    multiples of 8 and ascending (FlatSpace.segments()); total: numel of the
+    flat buffers (a multiple of 8). A chunk is a LARS_CHUNK piece of a
+    segment counted from the segment's start; its update extent runs to the
+    next chunk's start, so alignment gaps travel with the tensor in front of
+    them. A region (start, end) must begin at a segment start and end at one
+    (or at `total`): it then is a contiguous chunk and segment range."""
+
+    def __init__(self, segments, total: int, device=None):
+        segs = [(int(o), int(n), int(d)) for o, n, d in segments]
+        if not segs:
+            raise ValueError("LARS needs at least one segment")
+        total = int(total)
+        if total % LARS_ALIGN:
+            raise ValueError(f"flat numel {total} is no multiple of "
+                             f"{LARS_ALIGN}")
+        prev_end = 0
+        for o, n, d in segs:
+            if o % LARS_ALIGN or o < prev_end or n < 0:
+                raise ValueError(f"segment ({o}, {n}) is unaligned, "
+                                 "overlapping or out of order")
+            prev_end = o + n
+        if prev_end > total or segs[0][0] != 0:
+            raise ValueError("segments must start at 0 and fit the buffer")
+        self.segments = segs
+        self.total = total
+        self.device = torch.device(device) if device is not None \
+            else torch.device('cpu')
+        self.seg_offsets = [o for o, _, _ in segs]
+        starts, lens, cseg, seg_c0 = [], [], [], []
+        for s, (o, n, _) in enumerate(segs):
+            seg_c0.append(len(starts))
+            for c in range(0, n, LARS_CHUNK):
+                starts.append(o + c)
+                lens.append(min(LARS_CHUNK, n - c))
+                cseg.append(s)
+        seg_c0.append(len(starts))
+        starts.append(total)
+        if len(starts) - 1 >= 2 ** 31:
+            raise ValueError("too many chunks")
+        self.nseg, self.nchunk = len(segs), len(starts) - 1
+        self.seg_chunk0_host = seg_c0
+        dev = self.device
+        self.chunk_start = torch.tensor(starts, dtype=torch.int64, device=dev)
+        self.chunk_len = torch.tensor(lens, dtype=torch.int32, device=dev)
+        self.chunk_seg = torch.tensor(cseg, dtype=torch.int32, device=dev)
+        self.seg_chunk0 = torch.tensor(seg_c0, dtype=torch.int32, device=dev)
+        self.seg_adapt = torch.tensor([int(d > 1) for _, _, d in segs],
+                                      dtype=torch.int32, device=dev)
+        # workspaces: per-chunk (Sw, Sg) partials, per-segment sums and the
+        # per-segment step size / decay the update reads
+        self.partial = torch.zeros(max(self.nchunk, 1), 2,
+                                   dtype=torch.float64, device=dev)
+        self.seg_sums = torch.zeros(self.nseg, 2, dtype=torch.float64,
+                                    device=dev)
+        self.local_lr = torch.zeros(self.nseg, dtype=torch.float32, device=dev)
+        self.wd_seg = torch.zeros(self.nseg, dtype=torch.float32, device=dev)
+
+    def ranges(self, region=None):
+        """(seg0, seg1, chunk0, chunk1, start, end) of a region."""
+        import bisect
+        if region is None:
+            return 0, self.nseg, 0, self.nchunk, 0, self.total
+        st, en = int(region[0]), int(region[1])
+        s0 = bisect.bisect_left(self.seg_offsets, st)
+        s1 = (self.nseg if en == self.total
+              else bisect.bisect_left(self.seg_offsets, en))
+        if (s0 >= self.nseg or self.seg_offsets[s0] != st or st > en
+                or (en != self.total and (s1 >= self.nseg or
+                                          self.seg_offsets[s1] != en))):
+            raise ValueError(f"region {(st, en)} does not run from one "
+                             "parameter start to another")
+        return (s0, s1, self.seg_chunk0_host[s0], self.seg_chunk0_host[s1],
+                st, en)
+
+
+def _lars_check(layout: LarsLayout, w, g, m=None, wire_out=None) -> None:
+    if w.dtype != torch.float32:
+        raise TypeError("master weights must be f32")
+    if g.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError("the gradient sum must be f32 or bf16")
+    if m is not None and m.dtype != torch.float32:
+        raise TypeError("momentum must be f32")
+    for name, t in (("w", w), ("grad_sum", g), ("momentum_buf", m),
+                    ("wire_out", wire_out)):
+        if t is None:
+            continue
+        _check_flat(t, name, layout.total)
+        if t.device != layout.device:
+            raise ValueError(f"{name} is on {t.device}, the LARS layout on "
+                             f"{layout.device}")
+        if t.is_cuda and t.data_ptr() % 16:
+            raise ValueError(f"{name} must be 16-byte aligned")
+
+
+def lars_norms(layout: LarsLayout, w: torch.Tensor, grad_sum: torch.Tensor,
+               lr_table: torch.Tensor, step_ctr: torch.Tensor,
+               lr_cur: torch.Tensor, grad_scale: float = 1.0,
+               eta: float = 1e-3, weight_decay: float = 0.0,
+               eps: float = 0.0, region=None, advance: bool = True) -> None:
+    """Per-segment norms and step sizes of the region's segments into
+    layout.seg_sums / local_lr / wd_seg. w, grad_sum: the WHOLE flat buffers.
+    lr_table f32 [T], step_ctr i64 [1], lr_cur f32 [1] live on the layout's
+    device; advance latches lr_cur from the table and bumps step_ctr before
+    the step sizes are formed. No host sync on the GPU."""
+    _lars_check(layout, w, grad_sum)
+    if (lr_table.dtype != torch.float32 or step_ctr.dtype != torch.int64
+            or lr_cur.dtype != torch.float32 or lr_table.numel() < 1):
+        raise TypeError("lr_table/lr_cur must be f32 and step_ctr i64")
+    s0, s1, c0, c1, _, _ = layout.ranges(region)
+    if w.is_cuda:
+        if advance and c1 == c0:
+            raise ValueError("an advancing LARS step needs a non-empty region")
+        rc = require_lib().ps_lars_norms(
+            w.data_ptr(), grad_sum.data_ptr(), dtype_tag(grad_sum.dtype),
+            layout.chunk_start.data_ptr(), layout.chunk_len.data_ptr(),
+            c0, c1 - c0, layout.seg_chunk0.data_ptr(),
+            layout.seg_adapt.data_ptr(), s0, s1 - s0,
+            layout.partial.data_ptr(), layout.seg_sums.data_ptr(),
+            layout.local_lr.data_ptr(), layout.wd_seg.data_ptr(),
+            lr_table.data_ptr(), lr_table.numel(), step_ctr.data_ptr(),
+            lr_cur.data_ptr(), int(bool(advance)), float(grad_scale),
+            float(eta), float(weight_decay), float(eps),
+            current_stream_ptr())
+        if rc:
+            raise RuntimeError(f"ps_lars_norms launched nothing (code {rc})")
+        return
+    import math
+    import numpy as np
+    if advance:
+        i = min(max(int(step_ctr), 0), lr_table.numel() - 1)
+        lr_cur.copy_(lr_table[i:i + 1])
+        step_ctr += 1
+    lr = float(lr_cur)
+    gs, eta, wd, eps = (float(grad_scale), float(eta), float(weight_decay),
+                        float(eps))
+    for s in range(s0, s1):
+        off, n, ndim = layout.segments[s]
+        sw = float(w[off:off + n].to(torch.float64).square().sum())
+        sg = float(grad_sum[off:off + n].to(torch.float64).square().sum())
+        adapt = ndim > 1
+        wn, gn = math.sqrt(sw), gs * math.sqrt(sg)
+        ratio = 1.0
+        if adapt and wn > 0.0 and gn > 0.0:
+            ratio = eta * wn / (gn + wd * wn + eps)
+        layout.seg_sums[s, 0] = sw
+        layout.seg_sums[s, 1] = sg
+        layout.local_lr[s] = float(np.float32(lr * ratio))
+        layout.wd_seg[s] = float(np.float32(wd)) if adapt else 0.0
+
+
+def _fma32(a: torch.Tensor, b: torch.Tensor, c: torch.Tensor) -> torch.Tensor:
+    """f32 fma through float64: the product is exact there, the sum rounds to
+    f64 and then to f32 (at most one double-rounding ulp from fmaf)."""
+    return (a.to(torch.float64) * b.to(torch.float64)
+            + c.to(torch.float64)).to(torch.float32)
+
+
+def lars_step(layout: LarsLayout, w: torch.Tensor, grad_sum: torch.Tensor,
+              momentum_buf: torch.Tensor, momentum: float = 0.0,
+              grad_scale: float = 1.0,
+              wire_out: Optional[torch.Tensor] = None, region=None) -> None:
+    """The LARS update of the region (alignment gaps included) with the step
+    sizes lars_norms left in layout.local_lr / wd_seg. All tensors are the
+    WHOLE flat buffers."""
+    _lars_check(layout, w, grad_sum, momentum_buf, wire_out)
+    s0, s1, c0, c1, st, en = layout.ranges(region)
+    if w.is_cuda:
+        rc = require_lib().ps_lars_update(
+            w.data_ptr(), grad_sum.data_ptr(), momentum_buf.data_ptr(),
+            0 if wire_out is None else wire_out.data_ptr(),
+            dtype_tag(grad_sum.dtype),
+            dtype_tag(wire_out.dtype) if wire_out is not None else 0,
+            layout.chunk_start.data_ptr(), layout.chunk_seg.data_ptr(),
+            c0, c1 - c0, layout.local_lr.data_ptr(),
+            layout.wd_seg.data_ptr(), float(momentum), float(grad_scale),
+            current_stream_ptr())
+        if rc:
+            raise RuntimeError(f"ps_lars_update launched nothing (code {rc})")
+        return
+    scale = torch.tensor(float(grad_scale), dtype=torch.float32)
+    mu = torch.tensor(float(momentum), dtype=torch.float32)
+    for s in range(s0, s1):
+        a = layout.seg_offsets[s]
+        if not layout.segments[s][1]:
+            continue                     # an empty tensor owns no chunk
+        b = en
+        for o, n, _ in layout.segments[s + 1:s1]:
+            if n:
+                b = o
+                break
+        llr, wds = layout.local_lr[s], layout.wd_seg[s]
+        ws, ms = w[a:b], momentum_buf[a:b]
+        gk = grad_sum[a:b].to(torch.float32) * scale
+        if float(wds) != 0.0:
+            gk = _fma32(wds, ws, gk)
+        mk = _fma32(mu, ms, llr * gk)
+        ms.copy_(mk)
+        ws.copy_(ws - mk)
+    if wire_out is not None:
+        wire_out[st:en].copy_(w[st:en].to(wire_out.dtype))
+
+
 def pack_wire(dst: torch.Tensor, src: torch.Tensor) -> None:
     """Wire pack: f32 -> bf16 (the GPU 'compression' path, ref compression.py
     g_compress role) or plain copy when dtypes match."""

@@ -23,3 +23,20 @@ __device__ __forceinline__ void sgd_update_elem(
     float upd = nesterov ? fmaf(mu, mk, gk) : mk;
     w = fmaf(-lr, upd, w);
 }
+
+// Per-element arithmetic of the LARS update (lars.hip). The step size llr
+// (= lr * trust ratio) and the decay wds are per tensor, so the learning
+// rate is folded into the momentum buffer, as usual for LARS:
+//
+//   g = s * scale              (+ wds * w, one fma, only where wds != 0)
+//   m = fma(mu, m, llr * g)
+//   w = w - m
+__device__ __forceinline__ void lars_update_elem(
+    float& w, float& m, float s, float scale, float llr, float mu, float wds)
+{
+    float gk = s * scale;
+    if (wds != 0.0f) gk = fmaf(wds, w, gk);
+    float mk = fmaf(mu, m, llr * gk);
+    m = mk;
+    w = w - mk;
+}

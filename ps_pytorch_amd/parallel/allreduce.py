@@ -28,7 +28,7 @@ from ..ops.loss import cross_entropy as ps_cross_entropy
 
 from ..config import JobConfig, input_shape_of, num_classes_of
 from ..models import build_model
-from ..optim import FlatSGD
+from ..optim import build_optimizer
 from ..parallel.flat import FlatSpace, prep_model
 from ..utils.logging import get_logger
 
@@ -65,7 +65,11 @@ class AllReduceTrainer:
         if dist.is_initialized() and self.world > 1:
             dist.broadcast(self.flat.flat_w, src=0)
         self.master_w = self.flat.flat_w.detach().to(torch.float32).clone()
-        self.optimizer = FlatSGD(self.master_w, lr=cfg.lr, momentum=cfg.momentum)
+        # this engine runs the replicated FlatSGD whatever --optimizer says,
+        # except lars
+        name = 'lars' if getattr(cfg, 'optimizer', 'sgd') == 'lars' else 'sgd'
+        self.optimizer, self._host_lr = build_optimizer(
+            cfg, self.master_w, self.flat, name=name)
         if cfg.overlap:
             self._install_hooks()
 
@@ -131,6 +135,8 @@ class AllReduceTrainer:
         for w in self._works:
             w.wait()
         self._works.clear()
+        if self._host_lr is not None:
+            self._host_lr.tick()
         # replicated fused update: summed grads / world, re-pack live params
         self.optimizer.step(self.flat.flat_g, grad_scale=1.0 / self.world,
                             wire_out=self.flat.flat_w)

@@ -246,6 +246,12 @@ class FlatSpace:
             out[name] = self._view(flat, p, off, pid).detach().clone()
         return out
 
+    def segments(self) -> List[tuple]:
+        """(offset, numel, ndim) per parameter in flat order: what a
+        per-tensor optimizer (FlatLARS) needs to know of the layout."""
+        return [(off, p.numel(), p.dim())
+                for p, off in zip(self.params, self.offsets)]
+
     def layout_signature(self) -> Sequence:
         """Deterministic layout descriptor; ranks compare it at init to agree
         on bucket framing (replaces the reference's per-layer tag contract)."""

@@ -27,7 +27,7 @@ import torch.distributed as dist
 from ..config import JobConfig, input_shape_of, num_classes_of
 from ..models import build_model
 from ..ops import functional as ops_f
-from ..optim import FlatAdam, FlatSGD
+from ..optim import build_optimizer
 from ..parallel.flat import FlatSpace, prep_model
 from ..parallel.transport import ControlPlane, PSTransport
 from ..utils.checkpoint import save_model_step
@@ -101,11 +101,10 @@ class ParameterServer:
             logger.info('PS resumed parameters from step %d', cfg.resume_step)
         # f32 master copy + optimizer state in HBM
         self.master_w = self.flat.flat_w.detach().to(torch.float32).clone()
-        if self.optimizer_name == 'adam':
-            self.optimizer = FlatAdam(self.master_w, lr=cfg.lr)
-        else:
-            self.optimizer = FlatSGD(self.master_w, lr=cfg.lr,
-                                     momentum=cfg.momentum)
+        # host_lr drives optimizer.lr of sgd / adam under a non-constant
+        # --lr-schedule; lars reads its schedule on the device
+        self.optimizer, self._host_lr = build_optimizer(
+            cfg, self.master_w, self.flat, name=self.optimizer_name)
         # first broadcast payload
         self.transport.pack_weights_from(self.master_w)
         # pipelined-broadcast mode: step k's weights go out at the tail of
@@ -122,6 +121,8 @@ class ParameterServer:
     def step(self) -> None:
         """One synchronous step (mirrors DistributedWorker.train_step order)."""
         t = self.transport
+        if self._host_lr is not None:
+            self._host_lr.tick()
         if t.bcast_bucketed:
             return self._step_pipelined()
         t.broadcast_weights()

@@ -19,7 +19,7 @@ from .ops.loss import cross_entropy as ps_cross_entropy
 
 from .config import JobConfig, num_classes_of, input_shape_of
 from .models import build_model
-from .optim import FlatSGD, FlatAdam
+from .optim import build_optimizer
 from .parallel.flat import FlatSpace, prep_model
 from .ops.metrics import MetricAccumulator
 from .utils.logging import get_logger
@@ -60,11 +60,10 @@ class NNTrainer:
             load_model_step(net, cfg.train_dir, cfg.resume_step, strict=False)
         # f32 master copy + fused update; flat_g is the "wire" (local = trivially summed)
         self.master_w = self.flat.flat_w.detach().to(torch.float32).clone()
-        if getattr(cfg, 'optimizer', 'sgd') == 'adam':
-            self.optimizer = FlatAdam(self.master_w, lr=cfg.lr)
-        else:
-            self.optimizer = FlatSGD(self.master_w, lr=cfg.lr,
-                                     momentum=cfg.momentum)
+        # host_lr: the schedule driver of the by-value-lr optimizers (None
+        # for a constant schedule, and for lars, which reads it on device)
+        self.optimizer, self._host_lr = build_optimizer(cfg, self.master_w,
+                                                        self.flat)
         # steal mode on GPU: Ps ops write grads into flat_g directly (no
         # per-param AccumulateGrad add kernels); view mode on CPU
         self.flat.attach_grads(steal=(self.device.type == 'cuda'))
@@ -88,6 +87,8 @@ class NNTrainer:
         loss, _ = self._loss(data, target)
         loss.backward()
         self.flat.harvest_grads()   # steal mode: catch torch-fallback grads
+        if self._host_lr is not None:
+            self._host_lr.tick()
         # fused: master update + re-pack into the live (possibly bf16) params
         self.optimizer.step(self.flat.flat_g, grad_scale=1.0,
                             wire_out=self.flat.flat_w)
@@ -110,6 +111,8 @@ class NNTrainer:
     def enable_graph(self, example_x: torch.Tensor,
                      example_y: torch.Tensor) -> bool:
         if self.device.type != 'cuda':
+            return False
+        if self._refuse_graph():
             return False
         example_x = example_x.contiguous(memory_format=torch.channels_last) \
             if example_x.dim() == 4 else example_x
@@ -134,6 +137,21 @@ class NNTrainer:
             warnings.warn(f"hipGraph capture failed, staying eager: {e}")
             self._graph = None
             return False
+
+    def _refuse_graph(self) -> bool:
+        """The sgd / adam kernels take lr by value, so a captured step would
+        replay the learning rate of the capture for ever: with a
+        non-constant schedule stay eager (lars reads its schedule on the
+        device and captures)."""
+        if self._host_lr is None:
+            return False
+        import warnings
+        warnings.warn(f"--lr-schedule {self.cfg.lr_schedule} with "
+                      f"--optimizer {self.cfg.optimizer} cannot be captured "
+                      "into a graph (lr is a by-value kernel argument); "
+                      "staying eager. --optimizer lars follows the schedule "
+                      "under capture")
+        return True
 
     def graph_step(self, data: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
         """Replay the captured step on new data; returns the (device) loss
@@ -164,6 +182,8 @@ class NNTrainer:
 
     def enable_graph_loader(self, loader) -> bool:
         if self.device.type != 'cuda':
+            return False
+        if self._refuse_graph():
             return False
         ds = loader.dataset
         if ds.dtype != self.compute_dtype:
