@@ -5,6 +5,7 @@ import torch.nn as nn
 
 from .lenet import LeNet
 from .resnet import ResNet18, ResNet34, ResNet50, ResNet101, ResNet152
+from .resnext import ResNeXt29_32x4d, ResNeXt50_32x4d
 from .vgg import VGG11, VGG11_BN, VGG13, VGG13_BN, VGG16, VGG16_BN, VGG19, VGG19_BN
 from .vgg import REF_FACTORY, convert_reference_vgg_state_dict
 
@@ -15,6 +16,8 @@ _FACTORY = {
     'resnet50': ResNet50,
     'resnet101': ResNet101,
     'resnet152': ResNet152,
+    'resnext29_32x4d': ResNeXt29_32x4d,
+    'resnext50_32x4d': ResNeXt50_32x4d,
     # ref util.py:19 maps "VGG11" to vgg11_bn — keep that behavior;
     # the plain variants stay reachable as VGG11_plain etc.
     'vgg11': VGG11_BN,
@@ -53,6 +56,7 @@ def build_model(name: str, num_classes: int = 10, in_channels: int = 3) -> nn.Mo
 
 
 __all__ = ['build_model', 'LeNet', 'ResNet18', 'ResNet34', 'ResNet50',
-           'ResNet101', 'ResNet152', 'VGG11', 'VGG13', 'VGG16', 'VGG19',
+           'ResNet101', 'ResNet152', 'ResNeXt29_32x4d', 'ResNeXt50_32x4d',
+           'VGG11', 'VGG13', 'VGG16', 'VGG19',
            'VGG11_BN', 'VGG13_BN', 'VGG16_BN', 'VGG19_BN',
            'convert_reference_vgg_state_dict']

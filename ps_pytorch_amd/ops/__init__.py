@@ -108,6 +108,16 @@ def _try_load() -> None:
         lib.ps_conv_halo_variant.argtypes = [ctypes.c_int] + [
             ctypes.c_void_p] * 5 + [ctypes.c_int] * 8 + [ctypes.c_void_p]
         lib.ps_conv_halo_variant.restype = ctypes.c_int
+        # grouped convolution (conv_group.hip). fwd: x, w, bias, out, wimg /
+        # dgrad: dout, w, dx, wimg / wgrad: dout, x, partial, dw; then Nb,
+        # H, W, C, G, P, Q, R, stride, pad (wgrad: + split), stream; nonzero
+        # = outside the envelope, nothing launched
+        lib.ps_gconv_fwd.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_int] * 10 + [ctypes.c_void_p]
+        lib.ps_gconv_fwd.restype = ctypes.c_int
+        lib.ps_gconv_dgrad.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int] * 10 + [ctypes.c_void_p]
+        lib.ps_gconv_dgrad.restype = ctypes.c_int
+        lib.ps_gconv_wgrad.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int] * 11 + [ctypes.c_void_p]
+        lib.ps_gconv_wgrad.restype = ctypes.c_int
         lib.ps_conv_bias_grad.argtypes = [ctypes.c_void_p] * 3 + [
             ctypes.c_long, ctypes.c_int, ctypes.c_void_p]
         lib.ps_wt_transpose.argtypes = [ctypes.c_void_p, ctypes.c_void_p,

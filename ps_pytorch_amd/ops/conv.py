@@ -1,5 +1,6 @@
 """PsConv2d — NHWC implicit-GEMM MFMA convolution (ops/kernels/conv.hip for
-bf16, ops/kernels/conv_f32.hip for fp32).
+bf16, ops/kernels/conv_f32.hip for fp32, ops/kernels/conv_group.hip for
+grouped bf16).
 
 Replaces the MIOpen path the reference reaches through nn.Conv2d
 (ref: src/model_ops/resnet.py:19-97, lenet.py:19-33). GPU training path is
@@ -67,6 +68,44 @@ def _supported(x: torch.Tensor, w: torch.Tensor, stride, padding,
         return False
     R, S = w.shape[2], w.shape[3]
     return R <= 7 and S <= 7
+
+
+# A/B kill-switch of the grouped kernels (ops/kernels/conv_group.hip):
+# PS_GCONV=0 sends grouped convolutions back to torch/MIOpen.
+_GCONV = os.environ.get('PS_GCONV', '1') != '0'
+
+
+def _group_supported(x: torch.Tensor, w: torch.Tensor, stride, padding,
+                     dilation, groups) -> bool:
+    """The envelope of conv_group.hip: bf16 NHWC, groups > 1, C == K,
+    C % 64 == 0, C/G in {4, 8, 16, 32, 64}, square R <= 7, stride 1 or 2."""
+    if not (_ENABLED and _GCONV) or groups <= 1:
+        return False
+    if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.bfloat16
+            and w.dtype == torch.bfloat16):
+        return False
+    C, K = x.shape[1], w.shape[0]
+    if C != K or C % 64 or C % groups or w.shape[1] * groups != C:
+        return False
+    if C // groups not in (4, 8, 16, 32, 64):
+        return False
+    if dilation[0] != 1 or dilation[1] != 1:
+        return False
+    if stride[0] != stride[1] or padding[0] != padding[1]:
+        return False
+    if stride[0] not in (1, 2):
+        return False
+    return w.shape[2] == w.shape[3] and w.shape[2] <= 7
+
+
+def _gconv_wgrad_split(M: int, C: int, RS: int) -> int:
+    """Split factor of the grouped wgrad (conv_group.hip: one block per
+    (slab, tap, chunk)): ~2 blocks/CU on 256 CUs over C/64 * R*S tiles, at
+    least 64 pixels per chunk, at most 256 chunks. The kernel takes `split`
+    as given and rounds the chunk up to a multiple of 32 pixels."""
+    tiles = (C // 64) * RS
+    want = max(1, 512 // max(tiles, 1))
+    return max(1, min(want, max(1, M // 64), 256))
 
 
 def _wgrad_split(M: int, K: int, C: int, R: int, S: int,
@@ -395,6 +434,82 @@ class _ConvFn(torch.autograd.Function):
         return dx, dw, db, None, None
 
 
+class _GroupConvFn(torch.autograd.Function):
+    """Grouped bf16 convolution on conv_group.hip (envelope:
+    _group_supported). The expanded weight image is rebuilt by a small
+    kernel in every forward and backward; nothing is cached."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, stride, pad, groups):
+        lib = require_lib()
+        x = x.contiguous(memory_format=_CL)
+        wc = w.contiguous(memory_format=_CL)
+        Nb, C, H, W = x.shape
+        R = w.shape[2]
+        P = (H + 2 * pad - R) // stride + 1
+        Q = (W + 2 * pad - R) // stride + 1
+        sg = max(C // groups, 16)
+        out = torch.empty((Nb, C, P, Q), dtype=x.dtype, device=x.device,
+                          memory_format=_CL)
+        wimg = torch.empty(C * R * R * sg, dtype=x.dtype, device=x.device)
+        if lib.ps_gconv_fwd(x.data_ptr(), wc.data_ptr(),
+                            b.data_ptr() if b is not None else 0,
+                            out.data_ptr(), wimg.data_ptr(), Nb, H, W, C,
+                            groups, P, Q, R, stride, pad,
+                            current_stream_ptr()):
+            raise RuntimeError("ps_gconv_fwd rejected its arguments")
+        ctx.save_for_backward(x, wc)
+        ctx.conf = (stride, pad, groups, b is not None)
+        ctx.gtgt = (getattr(w, '_ps_flat_grad_fn', None),
+                    getattr(b, '_ps_flat_grad_fn', None) if b is not None else None)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = require_lib()
+        x, w = ctx.saved_tensors
+        stride, pad, groups, has_bias = ctx.conf
+        dout = dout.contiguous(memory_format=_CL)
+        Nb, C, H, W = x.shape
+        R = w.shape[2]
+        P, Q = dout.shape[2], dout.shape[3]
+        sg = max(C // groups, 16)
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty((Nb, C, H, W), dtype=x.dtype, device=x.device,
+                             memory_format=_CL)
+            wimg = torch.empty(C * R * R * sg, dtype=x.dtype, device=x.device)
+            if lib.ps_gconv_dgrad(dout.data_ptr(), w.data_ptr(),
+                                  dx.data_ptr(), wimg.data_ptr(), Nb, H, W,
+                                  C, groups, P, Q, R, stride, pad,
+                                  current_stream_ptr()):
+                raise RuntimeError("ps_gconv_dgrad rejected its arguments")
+        if ctx.needs_input_grad[1]:
+            split = _gconv_wgrad_split(Nb * P * Q, C, R * R)
+            partial = torch.empty(split * C * R * R * sg,
+                                  dtype=torch.float32, device=x.device)
+            wt_tgt = ctx.gtgt[0]() if ctx.gtgt[0] is not None else None
+            dw = (wt_tgt if wt_tgt is not None and wt_tgt.dtype == w.dtype
+                  and wt_tgt.is_cuda
+                  else torch.empty_like(w).contiguous(memory_format=_CL))
+            if lib.ps_gconv_wgrad(dout.data_ptr(), x.data_ptr(),
+                                  partial.data_ptr(), dw.data_ptr(), Nb, H,
+                                  W, C, groups, P, Q, R, stride, pad, split,
+                                  current_stream_ptr()):
+                raise RuntimeError("ps_gconv_wgrad rejected its arguments")
+        if has_bias and ctx.needs_input_grad[2]:
+            b_tgt = ctx.gtgt[1]() if ctx.gtgt[1] is not None else None
+            db = (b_tgt if b_tgt is not None and b_tgt.dtype == dout.dtype
+                  and b_tgt.is_cuda
+                  else torch.empty(C, dtype=dout.dtype, device=dout.device))
+            bpart = torch.empty(512 * C, dtype=torch.float32,
+                                device=dout.device)
+            lib.ps_conv_bias_grad(db.data_ptr(), dout.data_ptr(),
+                                  bpart.data_ptr(), Nb * P * Q, C,
+                                  current_stream_ptr())
+        return dx, dw, db, None, None, None
+
+
 class _ConvCarryFn(torch.autograd.Function):
     """Conv that also passes x through as a second output for the residual
     branch. At a ResNet block input, x feeds BOTH conv1 and the shortcut;
@@ -479,6 +594,10 @@ class PsConv2d(nn.Conv2d):
             if st is not None:
                 out._ps_bn_stats = st
             return out
+        if _group_supported(x, w, self.stride, self.padding, self.dilation,
+                            self.groups):
+            return _GroupConvFn.apply(x, w, b, self.stride[0],
+                                      self.padding[0], self.groups)
         if x.shape[1] != self.in_channels:   # fallback: drop pad channels
             x = x[:, :self.in_channels]
         return super().forward(x)
