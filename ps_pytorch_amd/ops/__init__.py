@@ -118,6 +118,16 @@ def _try_load() -> None:
         lib.ps_gconv_dgrad.restype = ctypes.c_int
         lib.ps_gconv_wgrad.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int] * 11 + [ctypes.c_void_p]
         lib.ps_gconv_wgrad.restype = ctypes.c_int
+        # depthwise convolution (conv_dw.hip), bf16 or f32 by dtype tag.
+        # fwd: x, w, bias, out / dgrad: dout, w, dx / wgrad: dout, x,
+        # partial, dw; then Nb, H, W, C, P, Q, R, stride, pad (wgrad: +
+        # split), dtype, stream; nonzero = outside the envelope, no launch
+        lib.ps_dwconv_fwd.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int] * 10 + [ctypes.c_void_p]
+        lib.ps_dwconv_fwd.restype = ctypes.c_int
+        lib.ps_dwconv_dgrad.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 10 + [ctypes.c_void_p]
+        lib.ps_dwconv_dgrad.restype = ctypes.c_int
+        lib.ps_dwconv_wgrad.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int] * 11 + [ctypes.c_void_p]
+        lib.ps_dwconv_wgrad.restype = ctypes.c_int
         lib.ps_conv_bias_grad.argtypes = [ctypes.c_void_p] * 3 + [
             ctypes.c_long, ctypes.c_int, ctypes.c_void_p]
         lib.ps_wt_transpose.argtypes = [ctypes.c_void_p, ctypes.c_void_p,

@@ -15,6 +15,12 @@ ARCH = os.environ.get("PS_ROCM_ARCH", "gfx950")
 
 SOURCES = sorted(KERNEL_DIR.glob("*.hip"))
 
+# f32 VALU kernels built without the packed-f32 instructions (v_pk_fma_f32
+# and kin): conv_dw.hip's contract is one scalar fma chain per output
+NO_PK_F32 = {"conv_dw.hip"}
+NO_PK_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+OBJ_DIR = OPS_DIR / "build"
+
 
 def _hipcc() -> str:
     for cand in (os.environ.get("HIPCC"), "/opt/rocm/bin/hipcc", "hipcc"):
@@ -34,14 +40,26 @@ def needs_build() -> bool:
 def build(verbose: bool = True, force: bool = False) -> Path:
     if not force and not needs_build():
         return SO_PATH
-    cmd = [
-        _hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17",
-        "-shared", "-fPIC", "-o", str(SO_PATH),
-    ] + [str(s) for s in SOURCES]
+    base = [_hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC"]
+    # sources of NO_PK_F32 are compiled on their own, to objects under
+    # build/ (git-ignored), and linked with the rest
+    objs = []
+    for src in SOURCES:
+        if src.name in NO_PK_F32:
+            OBJ_DIR.mkdir(exist_ok=True)
+            objs.append(OBJ_DIR / (src.stem + ".o"))
+            _run(base + NO_PK_FLAGS + ["-c", str(src), "-o", str(objs[-1])],
+                 verbose)
+    # objects first: hipcc reads every input after a .hip file as HIP source
+    _run(base + ["-shared", "-o", str(SO_PATH)] + [str(o) for o in objs]
+         + [str(s) for s in SOURCES if s.name not in NO_PK_F32], verbose)
+    return SO_PATH
+
+
+def _run(cmd, verbose: bool) -> None:
     if verbose:
         print("[ps_pytorch_amd.ops.build]", " ".join(cmd), file=sys.stderr)
     subprocess.run(cmd, check=True)
-    return SO_PATH
 
 
 if __name__ == "__main__":

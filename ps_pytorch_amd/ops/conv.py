@@ -1,6 +1,6 @@
 """PsConv2d — NHWC implicit-GEMM MFMA convolution (ops/kernels/conv.hip for
 bf16, ops/kernels/conv_f32.hip for fp32, ops/kernels/conv_group.hip for
-grouped bf16).
+grouped bf16, ops/kernels/conv_dw.hip for depthwise bf16 and fp32).
 
 Replaces the MIOpen path the reference reaches through nn.Conv2d
 (ref: src/model_ops/resnet.py:19-97, lenet.py:19-33). GPU training path is
@@ -19,7 +19,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import require_lib, current_stream_ptr
+from . import require_lib, current_stream_ptr, dtype_tag
 
 _CL = torch.channels_last
 
@@ -106,6 +106,45 @@ def _gconv_wgrad_split(M: int, C: int, RS: int) -> int:
     tiles = (C // 64) * RS
     want = max(1, 512 // max(tiles, 1))
     return max(1, min(want, max(1, M // 64), 256))
+
+
+# A/B kill-switch of the depthwise kernels (ops/kernels/conv_dw.hip):
+# PS_DWCONV=0 sends depthwise convolutions back to torch/MIOpen.
+_DWCONV = os.environ.get('PS_DWCONV', '1') != '0'
+
+
+def _dw_supported(x: torch.Tensor, w: torch.Tensor, stride, padding,
+                  dilation, groups) -> bool:
+    """The envelope of conv_dw.hip: bf16 or f32 NHWC, groups == C == K,
+    C % 8 == 0, square R in {3, 5, 7}, stride 1 or 2, padding < R."""
+    if not (_ENABLED and _DWCONV) or groups <= 1:
+        return False
+    if not (x.is_cuda and x.dim() == 4 and _dtype_ok(x.dtype)
+            and w.dtype == x.dtype):
+        return False
+    C, K = x.shape[1], w.shape[0]
+    if not (groups == C == K) or w.shape[1] != 1 or C % 8:
+        return False
+    if dilation[0] != 1 or dilation[1] != 1:
+        return False
+    if stride[0] != stride[1] or padding[0] != padding[1]:
+        return False
+    if stride[0] not in (1, 2):
+        return False
+    R = w.shape[2]
+    return w.shape[3] == R and R in (3, 5, 7) and 0 <= padding[0] < R
+
+
+def _dwconv_wgrad_split(M: int, C: int, R: int, slab: int = 64) -> int:
+    """Split factor of the depthwise wgrad (conv_dw.hip: one block per
+    (slab, tap-row group, chunk)): ~2 blocks/CU on 256 CUs over
+    ceil(C/slab) tiles (x R at R > 3, where a block takes one tap row), at
+    least 256 pixels per chunk, at most 256 chunks. `slab` is 64 channels
+    for bf16 and 32 for f32. The one place this rule lives: the kernel
+    takes `split` as given and deals its pixel tiles out in chunk order."""
+    tiles = -(-C // slab) * (1 if R == 3 else R)
+    want = max(1, 512 // max(tiles, 1))
+    return max(1, min(want, max(1, M // 256), 256))
 
 
 def _wgrad_split(M: int, K: int, C: int, R: int, S: int,
@@ -510,6 +549,79 @@ class _GroupConvFn(torch.autograd.Function):
         return dx, dw, db, None, None, None
 
 
+class _DwConvFn(torch.autograd.Function):
+    """Depthwise convolution on conv_dw.hip, bf16 or f32 (envelope:
+    _dw_supported). The weight is used in place as w[C][R*R]."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, stride, pad):
+        lib = require_lib()
+        x = x.contiguous(memory_format=_CL)
+        wc = w.contiguous()
+        Nb, C, H, W = x.shape
+        R = w.shape[2]
+        P = (H + 2 * pad - R) // stride + 1
+        Q = (W + 2 * pad - R) // stride + 1
+        out = torch.empty((Nb, C, P, Q), dtype=x.dtype, device=x.device,
+                          memory_format=_CL)
+        if lib.ps_dwconv_fwd(x.data_ptr(), wc.data_ptr(),
+                             b.data_ptr() if b is not None else 0,
+                             out.data_ptr(), Nb, H, W, C, P, Q, R, stride,
+                             pad, dtype_tag(x.dtype), current_stream_ptr()):
+            raise RuntimeError("ps_dwconv_fwd rejected its arguments")
+        ctx.save_for_backward(x, wc)
+        ctx.conf = (stride, pad, b is not None)
+        ctx.gtgt = (getattr(w, '_ps_flat_grad_fn', None),
+                    getattr(b, '_ps_flat_grad_fn', None) if b is not None else None)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = require_lib()
+        x, w = ctx.saved_tensors
+        stride, pad, has_bias = ctx.conf
+        dout = dout.contiguous(memory_format=_CL)
+        Nb, C, H, W = x.shape
+        R = w.shape[2]
+        P, Q = dout.shape[2], dout.shape[3]
+        tag = dtype_tag(x.dtype)
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty((Nb, C, H, W), dtype=x.dtype, device=x.device,
+                             memory_format=_CL)
+            if lib.ps_dwconv_dgrad(dout.data_ptr(), w.data_ptr(),
+                                   dx.data_ptr(), Nb, H, W, C, P, Q, R,
+                                   stride, pad, tag, current_stream_ptr()):
+                raise RuntimeError("ps_dwconv_dgrad rejected its arguments")
+        if ctx.needs_input_grad[1]:
+            split = _dwconv_wgrad_split(
+                Nb * P * Q, C, R, 64 if x.dtype == torch.bfloat16 else 32)
+            partial = torch.empty(split * R * R * C, dtype=torch.float32,
+                                  device=x.device)
+            wt_tgt = ctx.gtgt[0]() if ctx.gtgt[0] is not None else None
+            dw = (wt_tgt if wt_tgt is not None and wt_tgt.dtype == w.dtype
+                  and wt_tgt.is_cuda else torch.empty_like(w))
+            if lib.ps_dwconv_wgrad(dout.data_ptr(), x.data_ptr(),
+                                   partial.data_ptr(), dw.data_ptr(), Nb, H,
+                                   W, C, P, Q, R, stride, pad, split, tag,
+                                   current_stream_ptr()):
+                raise RuntimeError("ps_dwconv_wgrad rejected its arguments")
+        if has_bias and ctx.needs_input_grad[2]:
+            b_tgt = ctx.gtgt[1]() if ctx.gtgt[1] is not None else None
+            if x.dtype == torch.float32:
+                db = _f32_bias_grad(lib, dout, Nb * P * Q, C, b_tgt)
+            else:
+                db = (b_tgt if b_tgt is not None and b_tgt.dtype == dout.dtype
+                      and b_tgt.is_cuda
+                      else torch.empty(C, dtype=dout.dtype, device=dout.device))
+                bpart = torch.empty(512 * C, dtype=torch.float32,
+                                    device=dout.device)
+                lib.ps_conv_bias_grad(db.data_ptr(), dout.data_ptr(),
+                                      bpart.data_ptr(), Nb * P * Q, C,
+                                      current_stream_ptr())
+        return dx, dw, db, None, None
+
+
 class _ConvCarryFn(torch.autograd.Function):
     """Conv that also passes x through as a second output for the residual
     branch. At a ResNet block input, x feeds BOTH conv1 and the shortcut;
@@ -598,6 +710,9 @@ class PsConv2d(nn.Conv2d):
                             self.groups):
             return _GroupConvFn.apply(x, w, b, self.stride[0],
                                       self.padding[0], self.groups)
+        if _dw_supported(x, w, self.stride, self.padding, self.dilation,
+                         self.groups):
+            return _DwConvFn.apply(x, w, b, self.stride[0], self.padding[0])
         if x.shape[1] != self.in_channels:   # fallback: drop pad channels
             x = x[:, :self.in_channels]
         return super().forward(x)
