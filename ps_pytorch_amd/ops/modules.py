@@ -1,6 +1,7 @@
 """Fused NHWC BatchNorm(+residual)(+ReLU) module on the hand-written CDNA4
 kernels (ops/kernels/batchnorm.hip), with a torch fallback that doubles as
-the numerics reference (tests/test_bn_*).
+the numerics reference (tests/test_bn.py; the kernels are held to the float64
+oracle of tests/bn_utils.py by tests/test_bn_oracle_gpu.py).
 
 State-dict surface matches nn.BatchNorm2d (weight, bias, running_mean,
 running_var, num_batches_tracked) so checkpoints stay evaluator-compatible.
