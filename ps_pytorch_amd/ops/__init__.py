@@ -118,6 +118,14 @@ def _try_load() -> None:
         lib.ps_gconv_dgrad.restype = ctypes.c_int
         lib.ps_gconv_wgrad.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int] * 11 + [ctypes.c_void_p]
         lib.ps_gconv_wgrad.restype = ctypes.c_int
+        # f32 grouped convolution (conv_group_f32.hip): as above without
+        # the wimg argument; partial is split * C * R*R * Cg floats
+        lib.ps_gconv_fwd_f32.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int] * 10 + [ctypes.c_void_p]
+        lib.ps_gconv_fwd_f32.restype = ctypes.c_int
+        lib.ps_gconv_dgrad_f32.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 10 + [ctypes.c_void_p]
+        lib.ps_gconv_dgrad_f32.restype = ctypes.c_int
+        lib.ps_gconv_wgrad_f32.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int] * 11 + [ctypes.c_void_p]
+        lib.ps_gconv_wgrad_f32.restype = ctypes.c_int
         # depthwise convolution (conv_dw.hip), bf16 or f32 by dtype tag.
         # fwd: x, w, bias, out / dgrad: dout, w, dx / wgrad: dout, x,
         # partial, dw; then Nb, H, W, C, P, Q, R, stride, pad (wgrad: +

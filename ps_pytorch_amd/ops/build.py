@@ -16,8 +16,9 @@ ARCH = os.environ.get("PS_ROCM_ARCH", "gfx950")
 SOURCES = sorted(KERNEL_DIR.glob("*.hip"))
 
 # f32 VALU kernels built without the packed-f32 instructions (v_pk_fma_f32
-# and kin): conv_dw.hip's contract is one scalar fma chain per output
-NO_PK_F32 = {"conv_dw.hip"}
+# and kin): conv_dw.hip's contract is one scalar fma chain per output, and
+# conv_group_f32.hip's epilogue is scalar f32 adds
+NO_PK_F32 = {"conv_dw.hip", "conv_group_f32.hip"}
 NO_PK_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 OBJ_DIR = OPS_DIR / "build"
 

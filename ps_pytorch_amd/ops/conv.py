@@ -1,6 +1,7 @@
 """PsConv2d — NHWC implicit-GEMM MFMA convolution (ops/kernels/conv.hip for
 bf16, ops/kernels/conv_f32.hip for fp32, ops/kernels/conv_group.hip for
-grouped bf16, ops/kernels/conv_dw.hip for depthwise bf16 and fp32).
+grouped bf16, ops/kernels/conv_group_f32.hip for grouped fp32,
+ops/kernels/conv_dw.hip for depthwise bf16 and fp32).
 
 Replaces the MIOpen path the reference reaches through nn.Conv2d
 (ref: src/model_ops/resnet.py:19-97, lenet.py:19-33). GPU training path is
@@ -106,6 +107,45 @@ def _gconv_wgrad_split(M: int, C: int, RS: int) -> int:
     tiles = (C // 64) * RS
     want = max(1, 512 // max(tiles, 1))
     return max(1, min(want, max(1, M // 64), 256))
+
+
+def _group_f32_supported(x: torch.Tensor, w: torch.Tensor, stride, padding,
+                         dilation, groups) -> bool:
+    """The envelope of conv_group_f32.hip: that of _group_supported in f32
+    (PS_GCONV=0 or PS_F32=0 returns these convolutions to torch)."""
+    if not (_ENABLED and _GCONV and _F32) or groups <= 1:
+        return False
+    if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.float32
+            and w.dtype == torch.float32):
+        return False
+    C, K = x.shape[1], w.shape[0]
+    if C != K or C % 64 or C % groups or w.shape[1] * groups != C:
+        return False
+    if C // groups not in (4, 8, 16, 32, 64):
+        return False
+    if dilation[0] != 1 or dilation[1] != 1:
+        return False
+    if stride[0] != stride[1] or padding[0] != padding[1]:
+        return False
+    if stride[0] not in (1, 2):
+        return False
+    return w.shape[2] == w.shape[3] and w.shape[2] <= 7
+
+
+def _gconv_wgrad_split_f32(M: int, C: int, R: int, Cg: int) -> int:
+    """Split factor of the f32 grouped wgrad (conv_group_f32.hip), at least
+    64 pixels per chunk. Cg 4 / 8: one WAVE per (slab, chunk) holds all taps
+    of a 3x3 (per (slab, tap row, chunk) otherwise), so ~8 waves/CU on 256
+    CUs and at most 1024 chunks. Cg >= 16: one 256-thread block per (slab,
+    tap, chunk), ~2 blocks/CU, at most 256 chunks. The one place this rule
+    lives: the kernel takes `split` as given and rounds the chunk up to a
+    multiple of 16 pixels."""
+    if Cg <= 8:
+        tiles, target, cap = (C // 64) * (1 if R == 3 else R), 2048, 1024
+    else:
+        tiles, target, cap = (C // 64) * R * R, 512, 256
+    want = max(1, target // max(tiles, 1))
+    return max(1, min(want, max(1, M // 64), cap))
 
 
 # A/B kill-switch of the depthwise kernels (ops/kernels/conv_dw.hip):
@@ -549,6 +589,70 @@ class _GroupConvFn(torch.autograd.Function):
         return dx, dw, db, None, None, None
 
 
+class _GroupConvF32Fn(torch.autograd.Function):
+    """Grouped f32 convolution on conv_group_f32.hip (envelope:
+    _group_f32_supported). The weight is used in place as w[K][R][S][Cg];
+    there is no weight image."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, stride, pad, groups):
+        lib = require_lib()
+        x = x.contiguous(memory_format=_CL)
+        wc = w.contiguous(memory_format=_CL)
+        Nb, C, H, W = x.shape
+        R = w.shape[2]
+        P = (H + 2 * pad - R) // stride + 1
+        Q = (W + 2 * pad - R) // stride + 1
+        out = torch.empty((Nb, C, P, Q), dtype=x.dtype, device=x.device,
+                          memory_format=_CL)
+        if lib.ps_gconv_fwd_f32(x.data_ptr(), wc.data_ptr(),
+                                b.data_ptr() if b is not None else 0,
+                                out.data_ptr(), Nb, H, W, C, groups, P, Q, R,
+                                stride, pad, current_stream_ptr()):
+            raise RuntimeError("ps_gconv_fwd_f32 rejected its arguments")
+        ctx.save_for_backward(x, wc)
+        ctx.conf = (stride, pad, groups, b is not None)
+        ctx.gtgt = (getattr(w, '_ps_flat_grad_fn', None),
+                    getattr(b, '_ps_flat_grad_fn', None) if b is not None else None)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = require_lib()
+        x, w = ctx.saved_tensors
+        stride, pad, groups, has_bias = ctx.conf
+        dout = dout.contiguous(memory_format=_CL)
+        Nb, C, H, W = x.shape
+        R = w.shape[2]
+        P, Q = dout.shape[2], dout.shape[3]
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty((Nb, C, H, W), dtype=x.dtype, device=x.device,
+                             memory_format=_CL)
+            if lib.ps_gconv_dgrad_f32(dout.data_ptr(), w.data_ptr(),
+                                      dx.data_ptr(), Nb, H, W, C, groups, P,
+                                      Q, R, stride, pad,
+                                      current_stream_ptr()):
+                raise RuntimeError("ps_gconv_dgrad_f32 rejected its arguments")
+        if ctx.needs_input_grad[1]:
+            split = _gconv_wgrad_split_f32(Nb * P * Q, C, R, C // groups)
+            partial = torch.empty(split * w.numel(), dtype=torch.float32,
+                                  device=x.device)
+            wt_tgt = ctx.gtgt[0]() if ctx.gtgt[0] is not None else None
+            dw = (wt_tgt if wt_tgt is not None and wt_tgt.dtype == w.dtype
+                  and wt_tgt.is_cuda
+                  else torch.empty_like(w).contiguous(memory_format=_CL))
+            if lib.ps_gconv_wgrad_f32(dout.data_ptr(), x.data_ptr(),
+                                      partial.data_ptr(), dw.data_ptr(), Nb,
+                                      H, W, C, groups, P, Q, R, stride, pad,
+                                      split, current_stream_ptr()):
+                raise RuntimeError("ps_gconv_wgrad_f32 rejected its arguments")
+        if has_bias and ctx.needs_input_grad[2]:
+            b_tgt = ctx.gtgt[1]() if ctx.gtgt[1] is not None else None
+            db = _f32_bias_grad(lib, dout, Nb * P * Q, C, b_tgt)
+        return dx, dw, db, None, None, None
+
+
 class _DwConvFn(torch.autograd.Function):
     """Depthwise convolution on conv_dw.hip, bf16 or f32 (envelope:
     _dw_supported). The weight is used in place as w[C][R*R]."""
@@ -667,7 +771,9 @@ def conv_with_passthrough(mod: nn.Conv2d, x: torch.Tensor):
 class PsConv2d(nn.Conv2d):
     """nn.Conv2d whose GPU path runs the in-tree CDNA4 kernels: bf16 on
     conv.hip, fp32 on the exact-f32 MFMA family in conv_f32.hip (which
-    ignores out_pad and runs at the nominal channel counts).
+    ignores out_pad and runs at the nominal channel counts); grouped and
+    depthwise convolutions on conv_group.hip, conv_group_f32.hip and
+    conv_dw.hip.
 
     Ragged-channel pipelines (LeNet's 20 -> 50) can stay 8-aligned end to
     end via `out_pad` (plain attr, default 0, not in state_dict): on the
@@ -710,6 +816,10 @@ class PsConv2d(nn.Conv2d):
                             self.groups):
             return _GroupConvFn.apply(x, w, b, self.stride[0],
                                       self.padding[0], self.groups)
+        if _group_f32_supported(x, w, self.stride, self.padding,
+                                self.dilation, self.groups):
+            return _GroupConvF32Fn.apply(x, w, b, self.stride[0],
+                                         self.padding[0], self.groups)
         if _dw_supported(x, w, self.stride, self.padding, self.dilation,
                          self.groups):
             return _DwConvFn.apply(x, w, b, self.stride[0], self.padding[0])

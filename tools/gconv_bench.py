@@ -1,11 +1,13 @@
 #!/usr/bin/env python
 """Per-shape time of the grouped 3x3 convolutions of ResNeXt29_32x4d at the
-bench batch size: the in-tree kernels (ops/kernels/conv_group.hip) against
-PS_GCONV=0, i.e. torch/MIOpen, which is what PsConv2d(groups=G) ran on
-before the kernels existed.
+bench batch size: the in-tree kernels (ops/kernels/conv_group.hip, or
+ops/kernels/conv_group_f32.hip with --dtype fp32) against PS_GCONV=0, i.e.
+torch/MIOpen, which is what PsConv2d(groups=G) ran on before the kernels
+existed.
 
   python tools/gconv_bench.py [--batch 1024] [--iters 200] [--warmup 5]
-                              [--rounds 5]
+                              [--rounds 5] [--dtype {bf16,fp32}]
+                              [--net {resnext29,resnext50}]
 
 The model has nine grouped convolutions in five distinct shapes (the three
 blocks of a stage share one shape except the strided first block of stages
@@ -34,6 +36,8 @@ from ps_pytorch_amd.ops import require_lib  # noqa: E402
 
 # (C, H = W, stride) of the grouped convs; cardinality 32, 3x3, pad 1
 SHAPES = [(128, 32, 1), (256, 32, 2), (256, 16, 1), (512, 16, 2), (512, 8, 1)]
+# resnext50_32x4d on 32x32 inputs adds a fourth stage
+SHAPES50 = SHAPES + [(1024, 8, 2), (1024, 4, 1)]
 G = 32
 
 
@@ -69,13 +73,17 @@ def main(argv=None) -> None:
     ap.add_argument('--iters', type=int, default=200)
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--rounds', type=int, default=5)
+    ap.add_argument('--dtype', choices=('bf16', 'fp32'), default='bf16')
+    ap.add_argument('--net', choices=('resnext29', 'resnext50'),
+                    default='resnext29')
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("gconv_bench needs a GPU")
     require_lib()
-    bf, cl = torch.bfloat16, torch.channels_last
+    cl = torch.channels_last
+    bf = torch.bfloat16 if args.dtype == 'bf16' else torch.float32
     rows = []
-    for C, H, stride in SHAPES:
+    for C, H, stride in (SHAPES if args.net == 'resnext29' else SHAPES50):
         torch.manual_seed(C + H)
         conv = ps_conv.PsConv2d(C, C, 3, stride=stride, padding=1, groups=G,
                                 bias=False).to('cuda', bf)
@@ -113,7 +121,10 @@ def main(argv=None) -> None:
             'hand_bwd_tflops': round(2 * flop / med[True][1] / 1e6, 2),
             'max_err_vs_torch': [round(e, 5) for e in err]})
     ps_conv._GCONV = True
-    print(json.dumps({'bench': 'gconv', 'batch': args.batch,
+    extra = {} if args.dtype == 'bf16' else {'dtype': args.dtype}
+    if args.net != 'resnext29':
+        extra['net'] = args.net
+    print(json.dumps({'bench': 'gconv', **extra, 'batch': args.batch,
                       'iters': args.iters, 'rounds': args.rounds,
                       'device': torch.cuda.get_device_name(0), 'rows': rows}))
 
