@@ -1,6 +1,8 @@
 """Model zoo + factory (reference parity: src/util.py:8-19, src/model_ops/)."""
 from __future__ import annotations
 
+import functools
+
 import torch.nn as nn
 
 from .lenet import LeNet
@@ -18,6 +20,13 @@ _FACTORY = {
     'resnet50': ResNet50,
     'resnet101': ResNet101,
     'resnet152': ResNet152,
+    # GroupNorm (G = 32) in place of every BatchNorm: per-sample statistics,
+    # no running buffers (ops/kernels/groupnorm.hip)
+    'resnet18_gn': functools.partial(ResNet18, norm='gn'),
+    'resnet34_gn': functools.partial(ResNet34, norm='gn'),
+    'resnet50_gn': functools.partial(ResNet50, norm='gn'),
+    'resnet101_gn': functools.partial(ResNet101, norm='gn'),
+    'resnet152_gn': functools.partial(ResNet152, norm='gn'),
     'resnext29_32x4d': ResNeXt29_32x4d,
     'resnext50_32x4d': ResNeXt50_32x4d,
     # ref util.py:19 maps "VGG11" to vgg11_bn — keep that behavior;

@@ -170,6 +170,20 @@ def _try_load() -> None:
         lib.ps_bn_bwd.argtypes = [ctypes.c_void_p] * 12 + [
             ctypes.c_long, ctypes.c_long, ctypes.c_int, ctypes.c_int,
             ctypes.c_void_p]
+        # GroupNorm (groupnorm.hip). fwd: x, y, gamma, beta, res, mask, mean,
+        # invstd, ws, N, HW, C, G, eps, relu, slab, dtype, stream / bwd: x,
+        # mask, dy, gamma, mean, invstd, dx, dgamma, dbeta, dres, partial,
+        # ws, N, HW, C, G, relu, slab, dtype, stream; slab = _gn_plan's
+        # channels per block, 0 = streamed; nonzero = rejected, no launch
+        lib.ps_gn_fwd.argtypes = [ctypes.c_void_p] * 9 + [
+            ctypes.c_long] * 4 + [ctypes.c_float] + [ctypes.c_int] * 3 + [
+            ctypes.c_void_p]
+        lib.ps_gn_fwd.restype = ctypes.c_int
+        lib.ps_gn_bwd.argtypes = [ctypes.c_void_p] * 12 + [
+            ctypes.c_long] * 4 + [ctypes.c_int] * 3 + [ctypes.c_void_p]
+        lib.ps_gn_bwd.restype = ctypes.c_int
+        lib.ps_gn_ws_floats.argtypes = [ctypes.c_long] * 4
+        lib.ps_gn_ws_floats.restype = ctypes.c_long
         lib.ps_softmax_ce_fwd.argtypes = [ctypes.c_void_p] * 5 + [
             ctypes.c_long, ctypes.c_int, ctypes.c_void_p]
         lib.ps_softmax_ce_bwd.argtypes = [ctypes.c_void_p] * 5 + [

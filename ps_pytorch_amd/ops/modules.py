@@ -5,9 +5,13 @@ oracle of tests/bn_utils.py by tests/test_bn_oracle_gpu.py).
 
 State-dict surface matches nn.BatchNorm2d (weight, bias, running_mean,
 running_var, num_batches_tracked) so checkpoints stay evaluator-compatible.
+
+PsGroupNorm2d (below) is the GroupNorm counterpart on
+ops/kernels/groupnorm.hip, with nn.GroupNorm's state dict.
 """
 from __future__ import annotations
 
+import os
 from typing import Optional
 
 import torch
@@ -205,3 +209,179 @@ class PsBatchNorm2d(nn.Module):
     def extra_repr(self) -> str:
         return (f"{self.num_features}, eps={self.eps}, "
                 f"momentum={self.momentum}, relu={self.relu}")
+
+
+# ---------------------------------------------------------------- GroupNorm
+# Fused NHWC GroupNorm(+residual)(+ReLU) on ops/kernels/groupnorm.hip. The
+# statistics are per (sample, group): no running buffers, train() and eval()
+# run the same kernels, and a worker's shard of the batch changes nothing.
+
+_GN_CG = (2, 4, 8, 16, 32, 64)
+_GN_LDS_TILE_BUDGET = 64 * 1024
+
+
+def _gn_ok(x: torch.Tensor, num_groups: int) -> bool:
+    if not x.is_cuda or x.dim() != 4:
+        return False
+    C = x.shape[1]
+    return (C % 8 == 0 and C <= 2048 and C % num_groups == 0
+            and C // num_groups in _GN_CG and x.numel() > 0
+            and x.dtype in (torch.bfloat16, torch.float32))
+
+
+def _gn_plan(HW: int, C: int, Cg: int, elt_bytes: int, tiles: int) -> int:
+    """Channels per block (`slab`) of the sample-resident GroupNorm kernels,
+    or 0 for the streamed form. The only place this rule lives; the launch
+    functions take the result as given.
+
+    A block owns one sample x SC consecutive channels: SC is the smallest
+    count that holds whole groups, whole 16-B granules and whole mask octets,
+    divides C and spans at least `seg` bytes of every pixel (SC = C where C
+    itself is narrower). seg is tried at 128 B, then 64 B; a wider group
+    raises it to Cg * elt_bytes. The form is resident iff `tiles` [HW][SC]
+    tiles (1 forward, 2 backward: x and dy) fit the 64-KiB block budget and
+    the SC / (16 / elt_bytes) granule lanes fit one 256-thread block."""
+    vec = 16 // elt_bytes
+    unit = Cg if Cg % 8 == 0 else 8
+    for seg in (128, 64):
+        seg = max(seg, Cg * elt_bytes)
+        if C * elt_bytes <= seg:
+            sc = C
+        else:
+            sc = next(s for s in range(unit, C + 1, unit)
+                      if C % s == 0 and s * elt_bytes >= seg)
+        if (sc // vec <= 256
+                and tiles * HW * sc * elt_bytes <= _GN_LDS_TILE_BUDGET):
+            return sc
+    return 0
+
+
+class _FusedGNFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, gamma, beta, residual, num_groups, eps, relu, need_grad):
+        lib = require_lib()
+        x = x.contiguous(memory_format=_CL)
+        if residual is not None:
+            residual = residual.contiguous(memory_format=_CL)
+        N, C, H, W = x.shape
+        HW, G = H * W, num_groups
+        dev = x.device
+        slab = _gn_plan(HW, C, C // G, x.element_size(), 1)
+        y = torch.empty_like(x)
+        # resident form without a backward: no statistics, no mask written
+        stats = need_grad or not slab
+        save_mean = (torch.empty(N * G, dtype=torch.float32, device=dev)
+                     if stats else None)
+        save_invstd = torch.empty_like(save_mean) if stats else None
+        mask = (torch.empty(N * HW * (C // 8), dtype=torch.uint8, device=dev)
+                if relu and need_grad else None)
+        ws = (None if slab else torch.empty(
+            lib.ps_gn_ws_floats(N, HW, C, G), dtype=torch.float32, device=dev))
+        rc = lib.ps_gn_fwd(
+            x.data_ptr(), y.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+            residual.data_ptr() if residual is not None else 0,
+            mask.data_ptr() if mask is not None else 0,
+            save_mean.data_ptr() if stats else 0,
+            save_invstd.data_ptr() if stats else 0,
+            ws.data_ptr() if ws is not None else 0,
+            N, HW, C, G, float(eps), int(relu), slab,
+            dtype_tag(x.dtype), current_stream_ptr())
+        if rc:
+            raise RuntimeError(
+                f"ps_gn_fwd rejected N={N} HW={HW} C={C} G={G} slab={slab} "
+                f"{x.dtype} (rc={rc})")
+        if need_grad:
+            ctx.save_for_backward(x, gamma, save_mean, save_invstd)
+        ctx.mask = mask
+        ctx.relu = relu
+        ctx.G = G
+        ctx.has_res = residual is not None
+        # steal-mode flat_g targets (see parallel/flat.py attach_grads)
+        ctx.gtgt = (getattr(gamma, '_ps_flat_grad_fn', None),
+                    getattr(beta, '_ps_flat_grad_fn', None))
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = require_lib()
+        x, gamma, save_mean, save_invstd = ctx.saved_tensors
+        mask, G = ctx.mask, ctx.G
+        dy = dy.contiguous(memory_format=_CL)
+        N, C, H, W = x.shape
+        HW = H * W
+        dev = x.device
+        slab = _gn_plan(HW, C, C // G, x.element_size(), 2)
+        dx = torch.empty_like(x)
+        dres = torch.empty_like(x) if ctx.has_res else None
+        g_tgt = ctx.gtgt[0]() if ctx.gtgt[0] is not None else None
+        b_tgt = ctx.gtgt[1]() if ctx.gtgt[1] is not None else None
+        dgamma = (g_tgt if g_tgt is not None and g_tgt.dtype == gamma.dtype
+                  and g_tgt.is_cuda else torch.empty_like(gamma))
+        dbeta = (b_tgt if b_tgt is not None and b_tgt.dtype == gamma.dtype
+                 and b_tgt.is_cuda else torch.empty_like(gamma))
+        partial = torch.empty(N * 2 * C, dtype=torch.float32, device=dev)
+        ws = (None if slab else torch.empty(
+            lib.ps_gn_ws_floats(N, HW, C, G), dtype=torch.float32, device=dev))
+        rc = lib.ps_gn_bwd(
+            x.data_ptr(), mask.data_ptr() if mask is not None else 0,
+            dy.data_ptr(), gamma.data_ptr(), save_mean.data_ptr(),
+            save_invstd.data_ptr(), dx.data_ptr(), dgamma.data_ptr(),
+            dbeta.data_ptr(), dres.data_ptr() if dres is not None else 0,
+            partial.data_ptr(), ws.data_ptr() if ws is not None else 0,
+            N, HW, C, G, int(ctx.relu), slab, dtype_tag(x.dtype),
+            current_stream_ptr())
+        if rc:
+            raise RuntimeError(
+                f"ps_gn_bwd rejected N={N} HW={HW} C={C} G={G} slab={slab} "
+                f"{x.dtype} (rc={rc})")
+        return (dx, dgamma, dbeta, dres, None, None, None, None)
+
+
+class PsGroupNorm2d(nn.Module):
+    """GroupNorm over NCHW input with optional fused residual-add + ReLU.
+
+    forward(x, residual=None) == relu?(group_norm(x) + residual), the same in
+    train() and eval(). GPU path: the hand-written NHWC kernels of
+    groupnorm.hip; PS_GN=0, CPU tensors and shapes outside their envelope
+    (C % 8, C/G not in 2..64, C > 2048, non-4-D) take F.group_norm, which is
+    also the numerics reference. State dict: nn.GroupNorm's (weight, bias).
+    `kernel_calls` / `fallback_calls` count the forwards of either path.
+    """
+
+    def __init__(self, num_groups: int, num_channels: int, eps: float = 1e-5,
+                 relu: bool = False):
+        super().__init__()
+        if num_channels % num_groups:
+            raise ValueError("num_channels must be divisible by num_groups")
+        self.num_groups = num_groups
+        self.num_channels = num_channels
+        self.eps = eps
+        self.relu = relu
+        self.weight = nn.Parameter(torch.ones(num_channels))
+        self.bias = nn.Parameter(torch.zeros(num_channels))
+        self.kernel_calls = 0
+        self.fallback_calls = 0
+
+    def forward(self, x: torch.Tensor,
+                residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+        if (os.environ.get('PS_GN', '1') != '0' and _gn_ok(x, self.num_groups)
+                and self.weight.dtype == x.dtype):
+            self.kernel_calls += 1
+            need_grad = torch.is_grad_enabled() and (
+                x.requires_grad or self.weight.requires_grad
+                or self.bias.requires_grad
+                or (residual is not None and residual.requires_grad))
+            return _FusedGNFn.apply(x, self.weight, self.bias, residual,
+                                    self.num_groups, self.eps, self.relu,
+                                    need_grad)
+        self.fallback_calls += 1
+        y = F.group_norm(x, self.num_groups, self.weight, self.bias, self.eps)
+        if residual is not None:
+            y = y + residual
+        if self.relu:
+            y = F.relu(y)
+        return y
+
+    def extra_repr(self) -> str:
+        return (f"{self.num_groups}, {self.num_channels}, eps={self.eps}, "
+                f"relu={self.relu}")
