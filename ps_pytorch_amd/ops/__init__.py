@@ -108,6 +108,11 @@ def _try_load() -> None:
         lib.ps_conv_halo_variant.argtypes = [ctypes.c_int] + [
             ctypes.c_void_p] * 5 + [ctypes.c_int] * 8 + [ctypes.c_void_p]
         lib.ps_conv_halo_variant.restype = ctypes.c_int
+        # test hook, same arguments: variant 1 = conv3x3_halo_wide_kernel
+        # (3x3 s1 p1, >= 128 channels, W in 16 / 8 / 4)
+        lib.ps_conv_halo_wide_variant.argtypes = [ctypes.c_int] + [
+            ctypes.c_void_p] * 5 + [ctypes.c_int] * 8 + [ctypes.c_void_p]
+        lib.ps_conv_halo_wide_variant.restype = ctypes.c_int
         # grouped convolution (conv_group.hip). fwd: x, w, bias, out, wimg /
         # dgrad: dout, w, dx, wimg / wgrad: dout, x, partial, dw; then Nb,
         # H, W, C, G, P, Q, R, stride, pad (wgrad: + split), stream; nonzero

@@ -30,6 +30,11 @@
 //     conv3x3_halo_kernel: the block's halo patch is loaded once instead
 //     of once per tap, weights stream through a 3-stage LDS ring
 //     (PS_CONV_HALO=0: A/B against the generic kernel, bit-identical).
+//   * 128- / 256-channel 3x3 s1 p1 fwd/dgrad at W = 16 / 8 with whole
+//     128-pixel tiles (ResNet layers 2 and 3) take conv3x3_halo_wide_kernel:
+//     the same scheme at a 128x128 tile, the halo patches of all 64-channel
+//     chunks resident, the generic step order (PS_CONV_HALO_WIDE=0: A/B
+//     against the generic kernel, bit-identical).
 //   * stride is a template parameter; stride-2 dgrad runs by PARITY CLASS
 //     (conv_dgrad2_kernel, one launch for all four classes) at full tile
 //     density instead of predicating 3/4 of the MFMAs to zero.
@@ -896,6 +901,242 @@ __global__ __launch_bounds__(256) void conv3x3_halo_kernel(
 #pragma unroll
         for (int k2 = 0; k2 < 8; ++k2) o.us[k2] = f32_to_bf16(v[k2]);
         *(uint4*)&dst[om * 64 + segc] = o.u4;
+    }
+}
+
+// ------------------------- fwd / dgrad, 3x3 s1 p1, 128 / 256 channels wide
+//
+// conv_gemm_kernel<128,128> has the same nine-fold A re-fetch at the l2 / l3
+// body shapes (128 -> 128 at 16x16, 256 -> 256 at 8x8).
+// conv3x3_halo_wide_kernel is conv3x3_halo_kernel's scheme at a 128-pixel x
+// 128-column tile: the halo patches of ALL KC = Cin / 64 contraction chunks
+// are loaded once and stay in LDS (KC = 2 or 4), and the 9 * KC 16-KiB B
+// slices (128 columns x 64 channels of one tap and chunk) stream through
+// the same 3-stage ring (4 DMA pieces per wave and stage) in the generic
+// kernel's step order: taps outside, chunks inside.
+//
+// Pixel tile: NI pieces of 8 rows x W columns. W = 16: 8 rows of one image
+// (NI = 1); W = 8: two whole 8x8 images. Patch pixel
+// lp = i * PP + hr * (W + 2) + hc, PP = 10 (W + 2), holds input pixel
+// (h0_i - 1 + hr, hc - 1) of piece i, zero page outside the image and past
+// the patch (PWP pieces of 8 pixels per wave and chunk).
+//
+// Issue order: P0, B0, P1, B1, P2 .. P(KC-1), then B(g+2) after the barrier
+// of step g = tap * KC + chunk; all 9 * KC steps are unrolled. The waits
+// leave (KC-1) PWP + 4, (KC-2) PWP + 4, 4, 4, ... 4, 0 pieces outstanding:
+// step 0 starts when the first patch and slice have landed, the other
+// patches fly under it. No vmcnt(0) before the last step.
+// LDS: KC patches + 48 KB ring = 96 KB (W16, KC 2) .. 160 KB (W8, KC 4): one
+// block per CU. A 512-channel contraction (KC = 8) does not fit and stays
+// on the generic kernel, as does W = 4.
+//
+// Swizzle: position p of LDS row lp holds granule p ^ (((key >> 1) & 3) << 1)
+// with key = hr * W + hc (the pixel's index at pitch W, not W + 2). key and
+// lp have the same parity (W + 2 and PP are even), so a row's 16-B bank
+// class is 8 * (key & 1) + position. A 16-pixel fragment is W = 16: one
+// row, 16 hc; W = 8: two rows x 8 hc, from any hc base 0..2, and fragment
+// row f has key k0 + f at either width. In each ds_read_b128 lane group
+// (fragment rows {0-3, 12-15} at granule g, {4-11} at g ^ 1) key mod 8
+// takes all 8 values in either set. 16 lanes, 16 bank classes
+// (docs/KERNELS.md).
+//
+// Same MFMA, same lane layout, steps in (r, s, chunk) order with kk = 0, 1
+// inside, same f32 bias / carry add and single rounding as
+// conv_gemm_kernel: outputs are bit-identical to it.
+template <int W, int KC>
+struct HaloWideLds {
+    static constexpr int RT = 8;                    // rows per piece
+    static constexpr int NI = 128 / (RT * W);       // pieces per tile
+    static constexpr int HW2 = W + 2;
+    static constexpr int PP = (RT + 2) * HW2;       // patch pixels per piece
+    static constexpr int NPIX = NI * PP;
+    static constexpr int PWP = (NPIX + 31) / 32;    // patch DMA pieces per wave
+    unsigned short P[KC][PWP * 32][64];
+    unsigned short B[3][128][64];
+};
+
+template <int W, int KC, bool DGRAD, bool ACCF>
+__global__ __launch_bounds__(256) void conv3x3_halo_wide_kernel(
+    const unsigned short* __restrict__ src,  // fwd: in [Nb,H,W,C]; dgrad: dout [Nb,H,W,K]
+    const unsigned short* __restrict__ wgt,  // fwd: w [K,3,3,C]; dgrad: wT [3,3,C,K]
+    const unsigned short* __restrict__ bias, // [K] or null (fwd only)
+    unsigned short* __restrict__ dst,        // [Nb,H,W,Nout]
+    const unsigned short* __restrict__ carry,// [dst shape] (ACCF)
+    const unsigned short* __restrict__ zpage,
+    int H, int Nout)                         // output channels
+{
+    using L = HaloWideLds<W, KC>;
+    constexpr int Cin = KC * 64;                // contraction channels
+    constexpr int RT = L::RT, NI = L::NI, HW2 = L::HW2, PP = L::PP;
+    constexpr int NPIX = L::NPIX, PWP = L::PWP;
+    constexpr unsigned PBYTES = PWP * 32 * 128;
+    static_assert(sizeof(L) >= 128 * 128 * 4, "f32 staging fits LDS");
+    __shared__ __attribute__((aligned(128))) L lds;
+
+    const int t = threadIdx.x;
+    const int lane = t & 63, wid = t >> 6;
+    const int wm = wid >> 1, wn = wid & 1;
+    const int fr = lane & 15, fq = lane >> 4;
+    const int tiles_n = Nout >> 7;
+    const int tile_m = blockIdx.x / tiles_n;
+    const int n0 = (blockIdx.x - tile_m * tiles_n) * 128;
+    const long m0 = (long)tile_m * 128;
+    const int tpi = H / RT;                     // pieces per image
+
+    const int wu = __builtin_amdgcn_readfirstlane(wid);
+    const unsigned ldsP = (unsigned)(unsigned long)
+        (__attribute__((address_space(3))) void*)&lds.P[0][0][0];
+    const unsigned ldsB = (unsigned)(unsigned long)
+        (__attribute__((address_space(3))) void*)&lds.B[0][0][0];
+
+    // patch: piece gi = j*4 + wave covers pixels gi*8 + (lane>>3); poff is
+    // this lane's element offset in src at chunk 0, -1 = zero page
+    int poff[PWP];
+#pragma unroll
+    for (int j = 0; j < PWP; ++j) {
+        const int lp = (j * 4 + wu) * 8 + (lane >> 3);
+        const int i = lp / PP, rem = lp - i * PP;
+        const int hr = rem / HW2, hc = rem - hr * HW2;
+        const int gp = tile_m * NI + i;
+        const int n = gp / tpi;
+        const int h = (gp - n * tpi) * RT - 1 + hr, wc = hc - 1;
+        const bool ok = (lp < NPIX) & ((unsigned)h < (unsigned)H)
+                        & ((unsigned)wc < (unsigned)W);
+        const int key = hr * W + hc;
+        poff[j] = ok ? ((n * H + h) * W + wc) * Cin
+                       + (((lane & 7) ^ (((key >> 1) & 3) << 1)) * 8)
+                     : -1;
+    }
+    auto dma_p = [&](int c) {
+        const unsigned l = ldsP + c * PBYTES;
+#pragma unroll
+        for (int j = 0; j < PWP; ++j) {
+            const unsigned short* gs =
+                poff[j] >= 0 ? src + poff[j] + c * 64 : zpage;
+            halo_dma1(gs, l + (j * 4 + wu) * 1024);
+        }
+    };
+
+    // B: wave w stages rows (output columns) w*32 + rr*8 + (lane>>3)
+    const unsigned short* pB[4];
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) {
+        const int row = wid * 32 + rr * 8 + (lane >> 3);
+        pB[rr] = wgt + (long)(n0 + row) * (DGRAD ? Cin : 9 * Cin)
+                 + gswz<2>(row, lane & 7) * 8;
+    }
+    const long btap = DGRAD ? (long)Nout * Cin : Cin;   // elements between taps
+    auto dma_b = [&](int g) {                   // literal step only
+        const long o = (g / KC) * btap + (g % KC) * 64;
+        const unsigned l = ldsB + (g % 3) * 16384 + wu * 4096;
+        halo_dma2(pB[0] + o, pB[1] + o, l, l + 1024);
+        halo_dma2(pB[2] + o, pB[3] + o, l + 2048, l + 3072);
+    };
+
+    f32x4_t acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
+
+    // patch pixel and swizzle key of this lane's output row mi*16 + fr at
+    // shift (0,0)
+    int lp0[4], key0[4];
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi) {
+        const int o = wm * 64 + mi * 16 + fr;
+        const int i = o / (RT * W), oo = o - i * (RT * W);
+        lp0[mi] = i * PP + (oo / W) * HW2 + (oo % W);
+        key0[mi] = oo;                          // (oo / W) * W + oo % W
+    }
+    int brow[4];
+#pragma unroll
+    for (int nj = 0; nj < 4; ++nj) brow[nj] = wn * 64 + nj * 16 + fr;
+
+    auto mfma_step = [&](int g) {               // literal step only
+        const int tap = g / KC, c = g % KC;
+        const int r = tap / 3, s = tap % 3;
+        const int dr = DGRAD ? 2 - r : r, ds = DGRAD ? 2 - s : s;
+        const unsigned short (*pa)[64] = lds.P[c];
+        int lp[4], sw[4];
+#pragma unroll
+        for (int mi = 0; mi < 4; ++mi) {
+            lp[mi] = lp0[mi] + dr * HW2 + ds;
+            sw[mi] = (((key0[mi] + dr * W + ds) >> 1) & 3) << 1;
+        }
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) {
+            bf16x8_t a[4], b[4];
+#pragma unroll
+            for (int mi = 0; mi < 4; ++mi)
+                a[mi] = *(const bf16x8_t*)
+                    &pa[lp[mi]][((kk * 4 + fq) ^ sw[mi]) * 8];
+#pragma unroll
+            for (int nj = 0; nj < 4; ++nj)
+                b[nj] = *(const bf16x8_t*)
+                    &lds.B[g % 3][brow[nj]]
+                          [gswz<2>(brow[nj], kk * 4 + fq) * 8];
+#pragma unroll
+            for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+                for (int nj = 0; nj < 4; ++nj)
+                    acc[mi][nj] = MFMA_BF16(a[mi], b[nj], acc[mi][nj]);
+        }
+    };
+
+    constexpr int G = 9 * KC;                   // steps
+#pragma unroll
+    for (int c = 0; c < KC; ++c) {
+        dma_p(c);
+        if (c < 2) dma_b(c);
+    }
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        // retires: P0 + B0 | P1 + B1 | the other patches + B2 | B(g)
+        if (g == G - 1)  lds_ring_sync<0>();
+        else if (g == 0) lds_ring_sync<(KC - 1) * PWP + 4>();
+        else if (g == 1) lds_ring_sync<(KC - 2) * PWP + 4>();
+        else             lds_ring_sync<4>();
+        if (g + 2 < G) dma_b(g + 2);
+        mfma_step(g);
+    }
+    lds_ring_sync<0>();         // every wave done reading before the overlay
+
+    // ---- epilogue: conv_gemm_kernel's, at TM = TN = 128, full tiles ----
+    float* sf = reinterpret_cast<float*>(&lds);
+#pragma unroll
+    for (int nj = 0; nj < 4; ++nj) {
+        int cl = wn * 64 + nj * 16 + fr;
+        float bv = (!DGRAD && bias) ? bf16_to_f32(bias[n0 + cl]) : 0.f;
+#pragma unroll
+        for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            sf[(wm * 64 + mi * 16 + fq * 4 + e) * 128 + cl]
+                = acc[mi][nj][e] + bv;
+    }
+    __syncthreads();
+    const int segc = (t & 15) * 8;
+    const int rl0 = t >> 4;
+#pragma unroll
+    for (int ps = 0; ps < 8; ++ps) {
+        int rl = ps * 16 + rl0;
+        long om = m0 + rl;
+        f32x4_t a0 = *(const f32x4_t*)&sf[rl * 128 + segc];
+        f32x4_t a1 = *(const f32x4_t*)&sf[rl * 128 + segc + 4];
+        float v[8];
+#pragma unroll
+        for (int k2 = 0; k2 < 4; ++k2) { v[k2] = a0[k2]; v[4 + k2] = a1[k2]; }
+        V16 o;
+        if constexpr (ACCF) {
+            V16 cv = *(const V16*)&carry[om * Nout + n0 + segc];
+#pragma unroll
+            for (int k2 = 0; k2 < 8; ++k2)
+                v[k2] += bf16_to_f32(cv.us[k2]);
+        }
+#pragma unroll
+        for (int k2 = 0; k2 < 8; ++k2) o.us[k2] = f32_to_bf16(v[k2]);
+        *(uint4*)&dst[om * Nout + n0 + segc] = o.u4;
     }
 }
 
@@ -2602,6 +2843,64 @@ static inline bool halo_on() {
     return halo_mode() && glds_mode() && swz_mode() == 2;
 }
 
+// PS_CONV_HALO_WIDE=0 returns the 128- / 256-wide 3x3 shapes to conv_gemm_kernel
+// (A/B).
+static inline int halo_wide_mode() {
+    static int m = -1;
+    if (m < 0) { const char* e = getenv("PS_CONV_HALO_WIDE"); m = e ? atoi(e) : 1; }
+    return m;
+}
+
+// Shapes conv3x3_halo_wide_kernel takes: 3x3 stride 1 pad 1, a contraction
+// of 2 or 4 whole 64-channel chunks (all patches stay in LDS), whole
+// 128-column tiles, a 128-pixel tile that is 8 rows of one image (W = 16)
+// or two whole 8x8 images (W = 8) with no ragged M tile, int-sized offsets,
+// no BN-stats epilogue.
+static bool conv_halo_wide_eligible(bool dgrad, int Nb, int H, int W, int C,
+                                    int K, int P, int Q, int R, int S,
+                                    int stride, int pad, const void* stats)
+{
+    const int cin = dgrad ? K : C, nout = dgrad ? C : K;
+    if (!(R == 3 && S == 3 && stride == 1 && pad == 1 && P == H && Q == W
+          && stats == nullptr && Nb > 0))
+        return false;
+    if ((cin != 128 && cin != 256) || nout < 128 || nout % 128) return false;
+    if ((long)Nb * H * W * (cin > nout ? cin : nout) >= (1L << 31))
+        return false;
+    if (W == 16) return H > 0 && H % 8 == 0;
+    if (W == 8)  return H == 8 && Nb % 2 == 0;
+    return false;
+}
+
+// Both widths win in both ops (profiles/r18_conv_halo_wide.md), so the
+// dispatch gate is the switch alone.
+static inline bool halo_wide_on() { return halo_on() && halo_wide_mode(); }
+
+static void launch_conv_halo_wide(
+    bool dgrad, const void* src, const void* wgt, const void* bias,
+    void* dst, const void* carry, int Nb, int H, int W, int C, int K,
+    void* strm)
+{
+    const int cin = dgrad ? K : C, nout = dgrad ? C : K;
+    const long grid = (long)Nb * H * W / 128 * (nout / 128);
+#define HALOW(WV, KCV, DG, ACV)                                               \
+    hipLaunchKernelGGL((conv3x3_halo_wide_kernel<WV, KCV, DG, ACV>),          \
+        dim3((unsigned)grid), dim3(256), 0, (hipStream_t)strm,                \
+        (const unsigned short*)src, (const unsigned short*)wgt,               \
+        (const unsigned short*)bias, (unsigned short*)dst,                    \
+        (const unsigned short*)carry, zpage_ptr(), H, nout)
+#define HALOW_K(WV, DG, ACV) do { if (cin == 128) HALOW(WV, 2, DG, ACV);      \
+                                  else            HALOW(WV, 4, DG, ACV); } while (0)
+#define HALOW_W(DG, ACV) do { if (W == 16) HALOW_K(16, DG, ACV);              \
+                              else         HALOW_K(8, DG, ACV); } while (0)
+    if (!dgrad)     HALOW_W(false, false);
+    else if (carry) HALOW_W(true, true);
+    else            HALOW_W(true, false);
+#undef HALOW_W
+#undef HALOW_K
+#undef HALOW
+}
+
 extern "C" void ps_conv_fwd(
     const void* src, const void* wgt, const void* bias, void* dst,
     void* stats,
@@ -2611,6 +2910,11 @@ extern "C" void ps_conv_fwd(
     if (halo_on()
         && conv_halo_eligible(H, W, C, K, P, Q, R, S, stride, pad, stats))
         launch_conv_halo(false, src, wgt, bias, dst, nullptr, Nb, H, W, strm);
+    else if (halo_wide_on()
+             && conv_halo_wide_eligible(false, Nb, H, W, C, K, P, Q, R, S,
+                                        stride, pad, stats))
+        launch_conv_halo_wide(false, src, wgt, bias, dst, nullptr, Nb, H, W,
+                              C, K, strm);
     else
         conv_fwd_generic(src, wgt, bias, dst, stats, Nb, H, W, C, K, P, Q,
                          R, S, stride, pad, strm);
@@ -2624,6 +2928,11 @@ extern "C" void ps_conv_dgrad(
     if (halo_on()
         && conv_halo_eligible(H, W, C, K, P, Q, R, S, stride, pad, nullptr))
         launch_conv_halo(true, src, wgt, nullptr, dst, carry, Nb, H, W, strm);
+    else if (halo_wide_on()
+             && conv_halo_wide_eligible(true, Nb, H, W, C, K, P, Q, R, S,
+                                        stride, pad, nullptr))
+        launch_conv_halo_wide(true, src, wgt, nullptr, dst, carry, Nb, H, W,
+                              C, K, strm);
     else
         conv_dgrad_generic(src, wgt, dst, carry, Nb, H, W, C, K, P, Q,
                            R, S, stride, pad, strm);
@@ -2645,6 +2954,32 @@ extern "C" int ps_conv_halo_variant(
     if (variant == 1)
         launch_conv_halo(dgrad != 0, src, wgt, dgrad ? nullptr : bias, dst,
                          dgrad ? carry : nullptr, Nb, H, W, strm);
+    else if (dgrad)
+        conv_dgrad_generic(src, wgt, dst, carry, Nb, H, W, C, K, P, Q,
+                           3, 3, 1, 1, strm);
+    else
+        conv_fwd_generic(src, wgt, bias, dst, nullptr, Nb, H, W, C, K, P, Q,
+                         3, 3, 1, 1, strm);
+    return 0;
+}
+
+// Test hook with ps_conv_halo_variant's semantics for the wide kernel:
+// variant 0 = the conv_gemm_kernel the generic dispatch picks, 1 =
+// conv3x3_halo_wide_kernel. Nonzero and nothing launched for an ineligible
+// shape.
+extern "C" int ps_conv_halo_wide_variant(
+    int dgrad, const void* src, const void* wgt, const void* bias,
+    void* dst, const void* carry,
+    int Nb, int H, int W, int C, int K, int P, int Q, int variant, void* strm)
+{
+    if ((variant != 0 && variant != 1)
+        || !conv_halo_wide_eligible(dgrad != 0, Nb, H, W, C, K, P, Q, 3, 3,
+                                    1, 1, nullptr))
+        return 1;
+    if (variant == 1)
+        launch_conv_halo_wide(dgrad != 0, src, wgt, dgrad ? nullptr : bias,
+                              dst, dgrad ? carry : nullptr, Nb, H, W, C, K,
+                              strm);
     else if (dgrad)
         conv_dgrad_generic(src, wgt, dst, carry, Nb, H, W, C, K, P, Q,
                            3, 3, 1, 1, strm);

@@ -7,7 +7,9 @@ conflates the per-op numbers).
 
 Run on a GPU box:  python tools/conv_microbench.py [--batch 1024]
                    [--only "l1 64->64"]   (one shape alone, e.g. under both
-                                           values of PS_CONV_HALO)
+                                           values of PS_CONV_HALO or
+                                           PS_CONV_HALO_WIDE; _ for space)
+                   [--ps-only]            (no torch/MIOpen rows)
 """
 import argparse
 import sys
@@ -53,6 +55,7 @@ def select_shapes(only):
     if not only:
         return SHAPES
     names = [s[0] for s in SHAPES]
+    only = [o.replace('_', ' ') for o in only]  # l2_128->128 = "l2 128->128"
     for o in only:
         if o not in names:
             raise SystemExit(f"--only {o!r}: no such shape; have {names}")
@@ -65,6 +68,8 @@ def main():
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--only', action='append', default=None, metavar='NAME',
                     help='time only the shape with this name (repeatable)')
+    ap.add_argument('--ps-only', action='store_true',
+                    help='skip the torch/MIOpen rows')
     args = ap.parse_args()
     shapes = select_shapes(args.only)
     torch.backends.cudnn.benchmark = True
@@ -91,7 +96,7 @@ def main():
         flops = 2.0 * M * K * R * R * C
         strm = current_stream_ptr()
 
-        for impl in ('ps', 'miopen'):
+        for impl in ('ps',) if args.ps_only else ('ps', 'miopen'):
             if impl == 'ps':
                 def fwd():
                     lib.ps_conv_fwd(x.data_ptr(), w.data_ptr(), 0,

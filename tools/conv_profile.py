@@ -13,7 +13,9 @@ _CL = torch.channels_last
 
 SHAPES = {
     'l1': (64, 32, 32, 64, 3, 1, 1),
+    'l2': (128, 16, 16, 128, 3, 1, 1),
     'l3': (256, 8, 8, 256, 3, 1, 1),
+    'l4': (512, 4, 4, 512, 3, 1, 1),
     'stem': (3, 32, 32, 64, 3, 1, 1),
     'l2d': (64, 32, 32, 128, 3, 2, 1),
 }
