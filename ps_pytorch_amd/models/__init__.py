@@ -5,6 +5,7 @@ import functools
 
 import torch.nn as nn
 
+from .convnext import ConvNeXtSmall, ConvNeXtTiny
 from .lenet import LeNet
 from .mobilenet import MobileNet
 from .resnet import ResNet18, ResNet34, ResNet50, ResNet101, ResNet152
@@ -13,6 +14,9 @@ from .vgg import VGG11, VGG11_BN, VGG13, VGG13_BN, VGG16, VGG16_BN, VGG19, VGG19
 from .vgg import REF_FACTORY, convert_reference_vgg_state_dict
 
 _FACTORY = {
+    # depthwise 7x7 + LayerNorm / GELU / layer scale (ops/kernels/layernorm.hip)
+    'convnext_tiny': ConvNeXtTiny,
+    'convnext_small': ConvNeXtSmall,
     'lenet': LeNet,
     'mobilenet': MobileNet,
     'resnet18': ResNet18,
@@ -66,7 +70,7 @@ def build_model(name: str, num_classes: int = 10, in_channels: int = 3) -> nn.Mo
     return _FACTORY[key](num_classes=num_classes, in_channels=in_channels)
 
 
-__all__ = ['build_model', 'LeNet', 'MobileNet', 'ResNet18', 'ResNet34', 'ResNet50',
+__all__ = ['build_model', 'ConvNeXtTiny', 'ConvNeXtSmall', 'LeNet', 'MobileNet', 'ResNet18', 'ResNet34', 'ResNet50',
            'ResNet101', 'ResNet152', 'ResNeXt29_32x4d', 'ResNeXt50_32x4d',
            'VGG11', 'VGG13', 'VGG16', 'VGG19',
            'VGG11_BN', 'VGG13_BN', 'VGG16_BN', 'VGG19_BN',

@@ -189,6 +189,33 @@ def _try_load() -> None:
         lib.ps_gn_bwd.restype = ctypes.c_int
         lib.ps_gn_ws_floats.argtypes = [ctypes.c_long] * 4
         lib.ps_gn_ws_floats.restype = ctypes.c_long
+        # channel LayerNorm, GELU, layer scale (layernorm.hip). ln fwd: x, y,
+        # gamma, beta, mean, invstd, M, C, eps, rows_per_block, blocks,
+        # dtype, stream / ln bwd: x, dy, gamma, mean, invstd, dx, dgamma,
+        # dbeta, partial, M, C, rows_per_block, blocks, dtype, stream /
+        # gelu fwd: x, y, n, dtype, stream / gelu bwd: x, dy, dx, ... /
+        # lscale fwd: y, res, lambda, out, M, C, rows_per_block, blocks,
+        # dtype, stream / lscale bwd: y, dout, lambda, dy, dlambda, partial,
+        # ...; (rows_per_block, blocks) = _ln_plan's; nonzero = rejected
+        lib.ps_ln_fwd.argtypes = [ctypes.c_void_p] * 6 + [
+            ctypes.c_long] * 2 + [ctypes.c_float] + [ctypes.c_long] * 2 + [
+            ctypes.c_int, ctypes.c_void_p]
+        lib.ps_ln_fwd.restype = ctypes.c_int
+        lib.ps_ln_bwd.argtypes = [ctypes.c_void_p] * 9 + [
+            ctypes.c_long] * 4 + [ctypes.c_int, ctypes.c_void_p]
+        lib.ps_ln_bwd.restype = ctypes.c_int
+        lib.ps_gelu_fwd.argtypes = [ctypes.c_void_p] * 2 + [
+            ctypes.c_long, ctypes.c_int, ctypes.c_void_p]
+        lib.ps_gelu_fwd.restype = ctypes.c_int
+        lib.ps_gelu_bwd.argtypes = [ctypes.c_void_p] * 3 + [
+            ctypes.c_long, ctypes.c_int, ctypes.c_void_p]
+        lib.ps_gelu_bwd.restype = ctypes.c_int
+        lib.ps_lscale_fwd.argtypes = [ctypes.c_void_p] * 4 + [
+            ctypes.c_long] * 4 + [ctypes.c_int, ctypes.c_void_p]
+        lib.ps_lscale_fwd.restype = ctypes.c_int
+        lib.ps_lscale_bwd.argtypes = [ctypes.c_void_p] * 6 + [
+            ctypes.c_long] * 4 + [ctypes.c_int, ctypes.c_void_p]
+        lib.ps_lscale_bwd.restype = ctypes.c_int
         lib.ps_softmax_ce_fwd.argtypes = [ctypes.c_void_p] * 5 + [
             ctypes.c_long, ctypes.c_int, ctypes.c_void_p]
         lib.ps_softmax_ce_bwd.argtypes = [ctypes.c_void_p] * 5 + [

@@ -8,6 +8,9 @@ running_var, num_batches_tracked) so checkpoints stay evaluator-compatible.
 
 PsGroupNorm2d (below) is the GroupNorm counterpart on
 ops/kernels/groupnorm.hip, with nn.GroupNorm's state dict.
+
+PsLayerNorm2d, PsGELU and PsLayerScaleAdd (last section) are the steps of a
+ConvNeXt block between its convolutions, on ops/kernels/layernorm.hip.
 """
 from __future__ import annotations
 
@@ -385,3 +388,260 @@ class PsGroupNorm2d(nn.Module):
     def extra_repr(self) -> str:
         return (f"{self.num_groups}, {self.num_channels}, eps={self.eps}, "
                 f"relu={self.relu}")
+
+
+# ------------------------------------------- LayerNorm / GELU / layer scale
+# The steps of a ConvNeXt block between its convolutions, on
+# ops/kernels/layernorm.hip. PS_LN=0 sends all three back to torch.
+
+_LN_MAX_BLOCKS = 512      # about two blocks per CU on 256 CUs; also the cap
+_LN_MIN_PASSES = 8        # floor: passes of 256/LG rows a block walks
+
+
+def _ln_on() -> bool:
+    return os.environ.get('PS_LN', '1') != '0'
+
+
+def _ln_ok(x: torch.Tensor, *params: torch.Tensor) -> bool:
+    """The row kernels' envelope; params are the per-channel vectors, which
+    must be on x's device in x's type."""
+    if not (_ln_on() and x.is_cuda and x.dim() == 4 and x.numel() > 0):
+        return False
+    C = x.shape[1]
+    return (C % 8 == 0 and 8 <= C <= 2048
+            and x.dtype in (torch.bfloat16, torch.float32)
+            and all(p.dtype == x.dtype and p.device == x.device
+                    and p.numel() == C for p in params))
+
+
+def _vec16(t: torch.Tensor) -> torch.Tensor:
+    """t dense (4-D: channels_last, else row-major) and 16-B aligned, as the
+    kernels' 16-B accesses need; a dense view at an odd storage offset is
+    copied."""
+    t = t.contiguous(memory_format=_CL) if t.dim() == 4 else t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone(
+        memory_format=torch.preserve_format)
+
+
+def _ln_plan(M: int, C: int, elt_bytes: int):
+    """(rows_per_block, blocks) of the row kernels of layernorm.hip. The only
+    place this rule lives; the launch functions take the result as given.
+
+    A lane group of LG lanes (the smallest of 8, 16, 32, 64 that holds the
+    row's C / (16 / elt_bytes) granules, 64 above) owns a row, so a block
+    handles unit = 256 / LG rows at once. A block takes one contiguous chunk:
+    M spread over _LN_MAX_BLOCKS blocks (two per CU), but no fewer than
+    _LN_MIN_PASSES * unit rows, so that small inputs leave few partial rows
+    to fold; rounded up to a multiple of unit. blocks <= _LN_MAX_BLOCKS
+    bounds `partial` at 512 * 2 * C floats."""
+    gran = C // (16 // elt_bytes)
+    lg = next((v for v in (8, 16, 32) if v >= gran), 64)
+    unit = 256 // lg
+    want = max(_LN_MIN_PASSES * unit, -(-M // _LN_MAX_BLOCKS))
+    rpb = -(-want // unit) * unit
+    return rpb, -(-M // rpb)
+
+
+def _steal(fn, like: torch.Tensor) -> torch.Tensor:
+    """The flat-gradient slice of a parameter (parallel/flat.py attach_grads)
+    if it can take the kernel's output directly, else a fresh tensor."""
+    tgt = fn() if fn is not None else None
+    return (tgt if tgt is not None and tgt.dtype == like.dtype and tgt.is_cuda
+            and tgt.data_ptr() % 16 == 0 else torch.empty_like(like))
+
+
+class _FusedLNFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, gamma, beta, eps, need_grad):
+        lib = require_lib()
+        ctx.gtgt = (getattr(gamma, '_ps_flat_grad_fn', None),
+                    getattr(beta, '_ps_flat_grad_fn', None))
+        x, gamma, beta = _vec16(x), _vec16(gamma), _vec16(beta)
+        N, C, H, W = x.shape
+        M = N * H * W
+        y = torch.empty_like(x)
+        mean = (torch.empty(M, dtype=torch.float32, device=x.device)
+                if need_grad else None)
+        invstd = torch.empty_like(mean) if need_grad else None
+        rpb, blocks = _ln_plan(M, C, x.element_size())
+        rc = lib.ps_ln_fwd(
+            x.data_ptr(), y.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+            mean.data_ptr() if need_grad else 0,
+            invstd.data_ptr() if need_grad else 0,
+            M, C, float(eps), rpb, blocks, dtype_tag(x.dtype),
+            current_stream_ptr())
+        if rc:
+            raise RuntimeError(f"ps_ln_fwd rejected M={M} C={C} plan="
+                               f"{(rpb, blocks)} {x.dtype} (rc={rc})")
+        if need_grad:
+            ctx.save_for_backward(x, gamma, mean, invstd)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = require_lib()
+        x, gamma, mean, invstd = ctx.saved_tensors
+        dy = _vec16(dy)
+        N, C, H, W = x.shape
+        M = N * H * W
+        dx = torch.empty_like(x)
+        dgamma = _steal(ctx.gtgt[0], gamma)
+        dbeta = _steal(ctx.gtgt[1], gamma)
+        rpb, blocks = _ln_plan(M, C, x.element_size())
+        partial = torch.empty(blocks * 2 * C, dtype=torch.float32,
+                              device=x.device)
+        rc = lib.ps_ln_bwd(
+            x.data_ptr(), dy.data_ptr(), gamma.data_ptr(), mean.data_ptr(),
+            invstd.data_ptr(), dx.data_ptr(), dgamma.data_ptr(),
+            dbeta.data_ptr(), partial.data_ptr(), M, C, rpb, blocks,
+            dtype_tag(x.dtype), current_stream_ptr())
+        if rc:
+            raise RuntimeError(f"ps_ln_bwd rejected M={M} C={C} plan="
+                               f"{(rpb, blocks)} {x.dtype} (rc={rc})")
+        return dx, dgamma, dbeta, None, None
+
+
+class PsLayerNorm2d(nn.Module):
+    """LayerNorm over the channels of every pixel of an NCHW-logical 4-D
+    input (channels_last in memory), ConvNeXt's norm.
+
+    GPU path: layernorm.hip; PS_LN=0, CPU tensors and shapes outside the
+    envelope (C % 8, C > 2048, non-4-D) take F.layer_norm on the permuted
+    view, which is also the numerics reference. State dict: weight, bias.
+    `kernel_calls` / `fallback_calls` count the forwards of either path."""
+
+    def __init__(self, num_channels: int, eps: float = 1e-6):
+        super().__init__()
+        self.num_channels = num_channels
+        self.eps = eps
+        self.weight = nn.Parameter(torch.ones(num_channels))
+        self.bias = nn.Parameter(torch.zeros(num_channels))
+        self.kernel_calls = 0
+        self.fallback_calls = 0
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if _ln_ok(x, self.weight, self.bias):
+            self.kernel_calls += 1
+            need_grad = torch.is_grad_enabled() and (
+                x.requires_grad or self.weight.requires_grad
+                or self.bias.requires_grad)
+            return _FusedLNFn.apply(x, self.weight, self.bias, self.eps,
+                                    need_grad)
+        self.fallback_calls += 1
+        y = F.layer_norm(x.permute(0, 2, 3, 1), (self.num_channels,),
+                         self.weight, self.bias, self.eps)
+        return y.permute(0, 3, 1, 2)
+
+    def extra_repr(self) -> str:
+        return f"{self.num_channels}, eps={self.eps}"
+
+
+class _GELUFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        lib = require_lib()
+        x = _vec16(x)
+        y = torch.empty_like(x)
+        rc = lib.ps_gelu_fwd(x.data_ptr(), y.data_ptr(), x.numel(),
+                             dtype_tag(x.dtype), current_stream_ptr())
+        if rc:
+            raise RuntimeError(f"ps_gelu_fwd rejected n={x.numel()} {x.dtype}")
+        ctx.save_for_backward(x)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = require_lib()
+        (x,) = ctx.saved_tensors
+        dy = _vec16(dy)
+        dx = torch.empty_like(x)
+        rc = lib.ps_gelu_bwd(x.data_ptr(), dy.data_ptr(), dx.data_ptr(),
+                             x.numel(), dtype_tag(x.dtype),
+                             current_stream_ptr())
+        if rc:
+            raise RuntimeError(f"ps_gelu_bwd rejected n={x.numel()} {x.dtype}")
+        return dx
+
+
+class PsGELU(nn.Module):
+    """GELU in the exact erf form. GPU path: layernorm.hip's streaming
+    kernels (any shape with numel % 8 == 0; the backward recomputes from the
+    saved x); PS_LN=0, CPU tensors and other sizes take F.gelu."""
+
+    def __init__(self):
+        super().__init__()
+        self.kernel_calls = 0
+        self.fallback_calls = 0
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if (_ln_on() and x.is_cuda and x.numel() >= 8 and x.numel() % 8 == 0
+                and x.dtype in (torch.bfloat16, torch.float32)):
+            self.kernel_calls += 1
+            return _GELUFn.apply(x)
+        self.fallback_calls += 1
+        return F.gelu(x)
+
+
+class _LayerScaleAddFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y, res, lam):
+        lib = require_lib()
+        ctx.gtgt = getattr(lam, '_ps_flat_grad_fn', None)
+        y, res, lam = _vec16(y), _vec16(res), _vec16(lam)
+        N, C, H, W = y.shape
+        M = N * H * W
+        out = torch.empty_like(y)
+        rpb, blocks = _ln_plan(M, C, y.element_size())
+        rc = lib.ps_lscale_fwd(y.data_ptr(), res.data_ptr(), lam.data_ptr(),
+                               out.data_ptr(), M, C, rpb, blocks,
+                               dtype_tag(y.dtype), current_stream_ptr())
+        if rc:
+            raise RuntimeError(f"ps_lscale_fwd rejected M={M} C={C} plan="
+                               f"{(rpb, blocks)} {y.dtype} (rc={rc})")
+        ctx.save_for_backward(y, lam)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = require_lib()
+        y, lam = ctx.saved_tensors
+        dout = _vec16(dout)
+        N, C, H, W = y.shape
+        M = N * H * W
+        dy = torch.empty_like(y)
+        dlam = _steal(ctx.gtgt, lam)
+        rpb, blocks = _ln_plan(M, C, y.element_size())
+        partial = torch.empty(blocks * C, dtype=torch.float32, device=y.device)
+        rc = lib.ps_lscale_bwd(y.data_ptr(), dout.data_ptr(), lam.data_ptr(),
+                               dy.data_ptr(), dlam.data_ptr(),
+                               partial.data_ptr(), M, C, rpb, blocks,
+                               dtype_tag(y.dtype), current_stream_ptr())
+        if rc:
+            raise RuntimeError(f"ps_lscale_bwd rejected M={M} C={C} plan="
+                               f"{(rpb, blocks)} {y.dtype} (rc={rc})")
+        # the residual's gradient is dout itself, not a copy
+        return dy, dout, dlam
+
+
+class PsLayerScaleAdd(nn.Module):
+    """forward(y, residual) == residual + weight[c] * y: the tail of a
+    ConvNeXt block, `weight` the learned per-channel layer scale. GPU path:
+    layernorm.hip (4-D, C % 8 == 0, C <= 2048); otherwise torch ops."""
+
+    def __init__(self, num_channels: int, init: float = 1e-6):
+        super().__init__()
+        self.num_channels = num_channels
+        self.weight = nn.Parameter(torch.full((num_channels,), float(init)))
+        self.kernel_calls = 0
+        self.fallback_calls = 0
+
+    def forward(self, y: torch.Tensor, residual: torch.Tensor) -> torch.Tensor:
+        if (_ln_ok(y, self.weight) and residual.shape == y.shape
+                and residual.dtype == y.dtype and residual.device == y.device):
+            self.kernel_calls += 1
+            return _LayerScaleAddFn.apply(y, residual, self.weight)
+        self.fallback_calls += 1
+        return residual + self.weight.view(1, -1, 1, 1) * y
+
+    def extra_repr(self) -> str:
+        return f"{self.num_channels}"
