@@ -34,7 +34,9 @@
 //     128-pixel tiles (ResNet layers 2 and 3) take conv3x3_halo_wide_kernel:
 //     the same scheme at a 128x128 tile, the halo patches of all 64-channel
 //     chunks resident, the generic step order (PS_CONV_HALO_WIDE=0: A/B
-//     against the generic kernel, bit-identical).
+//     against the generic kernel, bit-identical). At 128 channels the
+//     weights stream in 8-KiB kk halves, so two blocks share a CU
+//     (PS_CONV_HALO_WIDE=1: the 16-KiB ring stages, one block per CU).
 //   * stride is a template parameter; stride-2 dgrad runs by PARITY CLASS
 //     (conv_dgrad2_kernel, one launch for all four classes) at full tile
 //     density instead of predicating 3/4 of the MFMAs to zero.
@@ -61,6 +63,7 @@
 //     dout/in come from that XCD's L2, not HBM.
 #include "common.h"
 #include <stdlib.h>
+#include <utility>
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef unsigned short ushort8_t __attribute__((ext_vector_type(8)));
@@ -943,7 +946,37 @@ __global__ __launch_bounds__(256) void conv3x3_halo_kernel(
 // Same MFMA, same lane layout, steps in (r, s, chunk) order with kk = 0, 1
 // inside, same f32 bias / carry add and single rounding as
 // conv_gemm_kernel: outputs are bit-identical to it.
-template <int W, int KC>
+//
+// The kk-split ring (SK = 32; profiles/r20_conv_halo_kkring.md). A ring
+// unit is one kk half of a step's slice, 128 columns x 32 channels = 8 KiB
+// (2 DMA pieces per wave), unit u = 2 * step + kk, NST stages, B(u + NST - 1)
+// issued after the barrier of unit u into the stage unit u - 1 read. With
+// KC = 2 the block then needs 48 / 56 KB of patches + 24 KB: two blocks per
+// CU, two waves per SIMD, so one block's barriers, prologue and epilogue
+// hide behind the other's MFMAs. SK = 64, NST = 3 is the ring above (KH = 1
+// unit per step).
+//
+// Both rings in one rule, KH = 64 / SK units per step, U = 9 KC KH units,
+// LA = NST - 1, DPS = SK / 16 pieces per wave and stage: the prologue
+// issues P0 .. P(KC-1) and, right after the patch of its chunk, each of the
+// units 0 .. LA-1 (SK = 32, NST = 3: P0, B0, B1, P1 ..; NST = 4: P0, B0,
+// B1, P1, B2, P2 ..). The wait of unit u leaves outstanding the units
+// issued after B(u), min(LA - 1, U - 1 - u) of them, and for u < LA the
+// KC - 1 - u / KH patches issued after it:
+//   SK 64 NST 3: (KC-1) PWP + 4, (KC-2) PWP + 4, 4, .., 4, 0
+//   SK 32 NST 3: (KC-1) PWP + 2, (KC-1) PWP + 2, 2, .., 2, 0
+//   SK 32 NST 4: (KC-1) PWP + 4, (KC-1) PWP + 4, (KC-2) PWP + 4, 4, .., 4, 2, 0
+// The 0 of the last unit is exact (nothing is issued after its slice).
+//
+// A 32-channel stage row is 64 B = 4 granules, 4 rows per 256-B bank line:
+// a row's 16-B bank class is 4 (row & 3) + position. Position p of row
+// holds granule p ^ bswz64(row), bswz64 = i ^ ((i & 1) << 1), i = (row >> 2)
+// & 3, i.e. 0, 3, 2, 1 for the four row quads of a 16-row fragment. A
+// ds_read_b128 lane group takes fragment rows {0-3, 12-15} at granule g and
+// {4-11} at g ^ 1: the four rows with the same row & 3 are quads 0 and 3 at
+// g, quads 1 and 2 at g ^ 1, positions g ^ {0, 1, 1 ^ 3, 1 ^ 2} = g ^ {0,
+// 1, 2, 3}. 16 lanes, 16 classes (docs/KERNELS.md).
+template <int W, int KC, int SK = 64, int NST = 3>
 struct HaloWideLds {
     static constexpr int RT = 8;                    // rows per piece
     static constexpr int NI = 128 / (RT * W);       // pieces per tile
@@ -952,11 +985,31 @@ struct HaloWideLds {
     static constexpr int NPIX = NI * PP;
     static constexpr int PWP = (NPIX + 31) / 32;    // patch DMA pieces per wave
     unsigned short P[KC][PWP * 32][64];
-    unsigned short B[3][128][64];
+    unsigned short B[NST][128][SK];
 };
 
-template <int W, int KC, bool DGRAD, bool ACCF>
-__global__ __launch_bounds__(256) void conv3x3_halo_wide_kernel(
+// XOR key of the 64-B stage rows of the kk-split ring (see above)
+__device__ __forceinline__ int bswz64(int row) {
+    const int i = (row >> 2) & 3;
+    return i ^ ((i & 1) << 1);
+}
+
+// f(integral_constant<int, 0>) .. f(integral_constant<int, N - 1>), in order
+template <typename F, int... I>
+__device__ __forceinline__ void static_for_seq(
+    F& f, std::integer_sequence<int, I...>) {
+    (f(std::integral_constant<int, I>{}), ...);
+}
+template <int N, typename F>
+__device__ __forceinline__ void static_for(F f) {
+    static_for_seq(f, std::make_integer_sequence<int, N>{});
+}
+
+// Two blocks per CU (160 KiB of LDS) where the block's LDS allows it.
+template <int W, int KC, bool DGRAD, bool ACCF, int SK = 64, int NST = 3>
+__global__ __launch_bounds__(
+    256, 2 * sizeof(HaloWideLds<W, KC, SK, NST>) <= 160 * 1024 ? 2 : 1)
+void conv3x3_halo_wide_kernel(
     const unsigned short* __restrict__ src,  // fwd: in [Nb,H,W,C]; dgrad: dout [Nb,H,W,K]
     const unsigned short* __restrict__ wgt,  // fwd: w [K,3,3,C]; dgrad: wT [3,3,C,K]
     const unsigned short* __restrict__ bias, // [K] or null (fwd only)
@@ -965,11 +1018,16 @@ __global__ __launch_bounds__(256) void conv3x3_halo_wide_kernel(
     const unsigned short* __restrict__ zpage,
     int H, int Nout)                         // output channels
 {
-    using L = HaloWideLds<W, KC>;
+    using L = HaloWideLds<W, KC, SK, NST>;
+    static_assert(SK == 32 || (SK == 64 && NST == 3), "ring shape");
     constexpr int Cin = KC * 64;                // contraction channels
     constexpr int RT = L::RT, NI = L::NI, HW2 = L::HW2, PP = L::PP;
     constexpr int NPIX = L::NPIX, PWP = L::PWP;
     constexpr unsigned PBYTES = PWP * 32 * 128;
+    constexpr int KH = 64 / SK;                 // ring units per step
+    constexpr int DPS = SK / 16;                // B pieces per wave and stage
+    constexpr int LA = NST - 1;                 // units in flight
+    constexpr unsigned SBYTES = 128 * SK * 2;   // stage
     static_assert(sizeof(L) >= 128 * 128 * 4, "f32 staging fits LDS");
     __shared__ __attribute__((aligned(128))) L lds;
 
@@ -1017,20 +1075,25 @@ __global__ __launch_bounds__(256) void conv3x3_halo_wide_kernel(
         }
     };
 
-    // B: wave w stages rows (output columns) w*32 + rr*8 + (lane>>3)
-    const unsigned short* pB[4];
+    // B: wave w stages rows (output columns) w*32 .. w*32 + 31, a 1-KiB
+    // piece is 8 rows of 8 granules (SK 64) or 16 rows of 4 (SK 32)
+    const unsigned short* pB[DPS];
 #pragma unroll
-    for (int rr = 0; rr < 4; ++rr) {
-        const int row = wid * 32 + rr * 8 + (lane >> 3);
+    for (int rr = 0; rr < DPS; ++rr) {
+        const int row = wid * 32
+                        + (SK == 64 ? rr * 8 + (lane >> 3) : rr * 16 + (lane >> 2));
         pB[rr] = wgt + (long)(n0 + row) * (DGRAD ? Cin : 9 * Cin)
-                 + gswz<2>(row, lane & 7) * 8;
+                 + (SK == 64 ? gswz<2>(row, lane & 7)
+                             : (lane & 3) ^ bswz64(row)) * 8;
     }
     const long btap = DGRAD ? (long)Nout * Cin : Cin;   // elements between taps
-    auto dma_b = [&](int g) {                   // literal step only
-        const long o = (g / KC) * btap + (g % KC) * 64;
-        const unsigned l = ldsB + (g % 3) * 16384 + wu * 4096;
+    auto dma_b = [&](int u) {                   // literal unit only
+        const int g = u / KH;
+        const long o = (g / KC) * btap + (g % KC) * 64 + (u % KH) * SK;
+        const unsigned l = ldsB + (u % NST) * SBYTES + wu * (SBYTES / 4);
         halo_dma2(pB[0] + o, pB[1] + o, l, l + 1024);
-        halo_dma2(pB[2] + o, pB[3] + o, l + 2048, l + 3072);
+        if constexpr (DPS == 4)
+            halo_dma2(pB[2] + o, pB[3] + o, l + 2048, l + 3072);
     };
 
     f32x4_t acc[4][4];
@@ -1053,7 +1116,8 @@ __global__ __launch_bounds__(256) void conv3x3_halo_wide_kernel(
 #pragma unroll
     for (int nj = 0; nj < 4; ++nj) brow[nj] = wn * 64 + nj * 16 + fr;
 
-    auto mfma_step = [&](int g) {               // literal step only
+    auto mfma_unit = [&](int u) {               // literal unit only
+        const int g = u / KH;
         const int tap = g / KC, c = g % KC;
         const int r = tap / 3, s = tap % 3;
         const int dr = DGRAD ? 2 - r : r, ds = DGRAD ? 2 - s : s;
@@ -1065,7 +1129,8 @@ __global__ __launch_bounds__(256) void conv3x3_halo_wide_kernel(
             sw[mi] = (((key0[mi] + dr * W + ds) >> 1) & 3) << 1;
         }
 #pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
+        for (int kk = (KH == 2 ? u % 2 : 0); kk < (KH == 2 ? u % 2 + 1 : 2);
+             ++kk) {
             bf16x8_t a[4], b[4];
 #pragma unroll
             for (int mi = 0; mi < 4; ++mi)
@@ -1074,8 +1139,9 @@ __global__ __launch_bounds__(256) void conv3x3_halo_wide_kernel(
 #pragma unroll
             for (int nj = 0; nj < 4; ++nj)
                 b[nj] = *(const bf16x8_t*)
-                    &lds.B[g % 3][brow[nj]]
-                          [gswz<2>(brow[nj], kk * 4 + fq) * 8];
+                    &lds.B[u % NST][brow[nj]]
+                          [(SK == 64 ? gswz<2>(brow[nj], kk * 4 + fq)
+                                     : fq ^ bswz64(brow[nj])) * 8];
 #pragma unroll
             for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
@@ -1084,22 +1150,25 @@ __global__ __launch_bounds__(256) void conv3x3_halo_wide_kernel(
         }
     };
 
-    constexpr int G = 9 * KC;                   // steps
+    constexpr int U = 9 * KC * KH;              // ring units
+    static_assert((LA - 1) / KH < KC, "prologue units follow their patch");
 #pragma unroll
     for (int c = 0; c < KC; ++c) {
         dma_p(c);
-        if (c < 2) dma_b(c);
-    }
 #pragma unroll
-    for (int g = 0; g < G; ++g) {
-        // retires: P0 + B0 | P1 + B1 | the other patches + B2 | B(g)
-        if (g == G - 1)  lds_ring_sync<0>();
-        else if (g == 0) lds_ring_sync<(KC - 1) * PWP + 4>();
-        else if (g == 1) lds_ring_sync<(KC - 2) * PWP + 4>();
-        else             lds_ring_sync<4>();
-        if (g + 2 < G) dma_b(g + 2);
-        mfma_step(g);
+        for (int u = 0; u < LA; ++u)
+            if (u / KH == c) dma_b(u);
     }
+    static_for<U>([&](auto uc) {
+        constexpr int u = decltype(uc)::value;
+        // still in flight after B(u): the later units and, in the prologue,
+        // the later patches
+        constexpr int nb = LA - 1 < U - 1 - u ? LA - 1 : U - 1 - u;
+        constexpr int np = u < LA ? KC - 1 - u / KH : 0;
+        lds_ring_sync<nb * DPS + np * PWP>();
+        if constexpr (u + LA < U) dma_b(u + LA);
+        mfma_unit(u);
+    });
     lds_ring_sync<0>();         // every wave done reading before the overlay
 
     // ---- epilogue: conv_gemm_kernel's, at TM = TN = 128, full tiles ----
@@ -2843,11 +2912,12 @@ static inline bool halo_on() {
     return halo_mode() && glds_mode() && swz_mode() == 2;
 }
 
-// PS_CONV_HALO_WIDE=0 returns the 128- / 256-wide 3x3 shapes to conv_gemm_kernel
-// (A/B).
+// PS_CONV_HALO_WIDE=0 returns the 128- / 256-wide 3x3 shapes to conv_gemm_kernel,
+// 1 keeps conv3x3_halo_wide_kernel on its 16-KiB ring stages (both A/B);
+// unset or 2: the ring halo_wide_ring() picks per shape.
 static inline int halo_wide_mode() {
     static int m = -1;
-    if (m < 0) { const char* e = getenv("PS_CONV_HALO_WIDE"); m = e ? atoi(e) : 1; }
+    if (m < 0) { const char* e = getenv("PS_CONV_HALO_WIDE"); m = e ? atoi(e) : 2; }
     return m;
 }
 
@@ -2876,21 +2946,30 @@ static bool conv_halo_wide_eligible(bool dgrad, int Nb, int H, int W, int C,
 // dispatch gate is the switch alone.
 static inline bool halo_wide_on() { return halo_on() && halo_wide_mode(); }
 
+// ring 1 = 16-KiB stages, 2 = the kk-split 8-KiB stages (3 of them). The
+// kk-split ring exists for the 128-channel contraction, where it lets two
+// blocks share a CU; at 256 channels one block fits either way and the finer
+// ring measured 5 us slower (profiles/r20_conv_halo_kkring.md).
+static inline bool halo_wide_has_kk(int cin) { return cin == 128; }
+
 static void launch_conv_halo_wide(
     bool dgrad, const void* src, const void* wgt, const void* bias,
     void* dst, const void* carry, int Nb, int H, int W, int C, int K,
-    void* strm)
+    int ring, void* strm)
 {
     const int cin = dgrad ? K : C, nout = dgrad ? C : K;
     const long grid = (long)Nb * H * W / 128 * (nout / 128);
-#define HALOW(WV, KCV, DG, ACV)                                               \
-    hipLaunchKernelGGL((conv3x3_halo_wide_kernel<WV, KCV, DG, ACV>),          \
+    const bool kk = ring == 2 && halo_wide_has_kk(cin);
+#define HALOW_R(WV, KCV, DG, ACV, SKV)                                        \
+    hipLaunchKernelGGL((conv3x3_halo_wide_kernel<WV, KCV, DG, ACV, SKV, 3>),  \
         dim3((unsigned)grid), dim3(256), 0, (hipStream_t)strm,                \
         (const unsigned short*)src, (const unsigned short*)wgt,               \
         (const unsigned short*)bias, (unsigned short*)dst,                    \
         (const unsigned short*)carry, zpage_ptr(), H, nout)
-#define HALOW_K(WV, DG, ACV) do { if (cin == 128) HALOW(WV, 2, DG, ACV);      \
-                                  else            HALOW(WV, 4, DG, ACV); } while (0)
+#define HALOW_K(WV, DG, ACV) do {                                             \
+        if (kk)              HALOW_R(WV, 2, DG, ACV, 32);                     \
+        else if (cin == 128) HALOW_R(WV, 2, DG, ACV, 64);                     \
+        else                 HALOW_R(WV, 4, DG, ACV, 64); } while (0)
 #define HALOW_W(DG, ACV) do { if (W == 16) HALOW_K(16, DG, ACV);              \
                               else         HALOW_K(8, DG, ACV); } while (0)
     if (!dgrad)     HALOW_W(false, false);
@@ -2898,7 +2977,14 @@ static void launch_conv_halo_wide(
     else            HALOW_W(true, false);
 #undef HALOW_W
 #undef HALOW_K
-#undef HALOW
+#undef HALOW_R
+}
+
+// The ring PS_CONV_HALO_WIDE's default (unset or 2) gives a shape: whichever
+// measured faster (profiles/r20_conv_halo_kkring.md).
+static inline int halo_wide_ring(int cin) {
+    if (halo_wide_mode() == 1) return 1;
+    return halo_wide_has_kk(cin) ? 2 : 1;
 }
 
 extern "C" void ps_conv_fwd(
@@ -2914,7 +3000,7 @@ extern "C" void ps_conv_fwd(
              && conv_halo_wide_eligible(false, Nb, H, W, C, K, P, Q, R, S,
                                         stride, pad, stats))
         launch_conv_halo_wide(false, src, wgt, bias, dst, nullptr, Nb, H, W,
-                              C, K, strm);
+                              C, K, halo_wide_ring(C), strm);
     else
         conv_fwd_generic(src, wgt, bias, dst, stats, Nb, H, W, C, K, P, Q,
                          R, S, stride, pad, strm);
@@ -2932,7 +3018,7 @@ extern "C" void ps_conv_dgrad(
              && conv_halo_wide_eligible(true, Nb, H, W, C, K, P, Q, R, S,
                                         stride, pad, nullptr))
         launch_conv_halo_wide(true, src, wgt, nullptr, dst, carry, Nb, H, W,
-                              C, K, strm);
+                              C, K, halo_wide_ring(K), strm);
     else
         conv_dgrad_generic(src, wgt, dst, carry, Nb, H, W, C, K, P, Q,
                            R, S, stride, pad, strm);
@@ -2965,21 +3051,22 @@ extern "C" int ps_conv_halo_variant(
 
 // Test hook with ps_conv_halo_variant's semantics for the wide kernel:
 // variant 0 = the conv_gemm_kernel the generic dispatch picks, 1 =
-// conv3x3_halo_wide_kernel. Nonzero and nothing launched for an ineligible
-// shape.
+// conv3x3_halo_wide_kernel on 16-KiB ring stages, 2 = on the kk-split ring.
+// Nonzero and nothing launched for a shape the variant does not take.
 extern "C" int ps_conv_halo_wide_variant(
     int dgrad, const void* src, const void* wgt, const void* bias,
     void* dst, const void* carry,
     int Nb, int H, int W, int C, int K, int P, int Q, int variant, void* strm)
 {
-    if ((variant != 0 && variant != 1)
+    if (variant < 0 || variant > 2
         || !conv_halo_wide_eligible(dgrad != 0, Nb, H, W, C, K, P, Q, 3, 3,
-                                    1, 1, nullptr))
+                                    1, 1, nullptr)
+        || (variant == 2 && !halo_wide_has_kk(dgrad ? K : C)))
         return 1;
-    if (variant == 1)
+    if (variant != 0)
         launch_conv_halo_wide(dgrad != 0, src, wgt, dgrad ? nullptr : bias,
                               dst, dgrad ? carry : nullptr, Nb, H, W, C, K,
-                              strm);
+                              variant, strm);
     else if (dgrad)
         conv_dgrad_generic(src, wgt, dst, carry, Nb, H, W, C, K, P, Q,
                            3, 3, 1, 1, strm);
